@@ -17,14 +17,22 @@ Queries shard across ranks with no data-path collective (weak scaling: per-GPU w
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 5 --warmup 2
 
-Rank 0 prints ONE JSON line.  `roofline` is measured on the dominant kernel (the MFMA GEMM):
-algorithmic flops of every GEMM launch of one step / summed launch durations, from HIP events
-recorded on the launch stream in an instrumented step after the timed region.  `cpu_baseline` is
-the CPU oracle (a port of the reference's op sequence, fp32) on a bounded sample, rank 0, N=1 only.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times `--steps` steps and prints the headline
+(`value`, `ms_per_step`, the workload's `config`, the algorithmic rate derived from them); `--dump-outputs DIR` then
+also writes the last timed step's sorted scores as DIR/<name>.npy (inputs are seeded: identical from run to run).
+`--full` adds the side measurements, each of which runs work of its own after the timed region:
+`roofline` on the dominant kernel (the MFMA GEMM): algorithmic flops of every GEMM launch of one step / summed
+launch durations, from HIP events recorded on the launch stream in an instrumented step; the device's clocks
+and power sampled during the timed region; `rank_fidelity` (the step re-run in the exact mode); the
+`precision_table` (the step at the other precisions); `cpu_baseline`, the CPU oracle (a port of the
+reference's op sequence, fp32) on a bounded sample, rank 0, N=1 only.
+
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -585,9 +593,12 @@ def train_mode(args, m2, m1, dev, dt):
 def launch_ranks(n: int) -> int:
     """Start one child process per GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in its environment, rendezvous on 127.0.0.1)
     running this same command line, let them write to this process's stdout / stderr (rank 0 alone prints the JSON line) and
-    return the first non-zero exit code (0 if every rank succeeded).  The launcher itself makes no GPU call."""
+    return the first non-zero exit code in time (0 if every rank succeeded): one thread per child waits for it and stamps its end,
+    so a rank that fails on its own is reported, not a peer whose collective failed a moment later because of it.  The launcher
+    itself makes no GPU call."""
     import socket
     import subprocess
+    import threading
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -596,20 +607,29 @@ def launch_ranks(n: int) -> int:
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
-    rc, failed_at = 0, None
-    while any(p.poll() is None for p in procs):
-        for p in procs:
-            if p.poll() not in (None, 0) and rc == 0:
-                rc, failed_at = p.returncode, time.time()
+    ended = {}                                                            # rank -> (time its process ended, exit code)
+
+    def reap(r):
+        code = procs[r].wait()
+        ended[r] = (time.monotonic(), code)
+
+    reapers = [threading.Thread(target=reap, args=(r,), daemon=True) for r in range(n)]
+    for t in reapers:
+        t.start()
+    failed_at = None
+    while any(t.is_alive() for t in reapers):
+        if failed_at is None and any(code != 0 for _, code in list(ended.values())):
+            failed_at = time.time()
         if failed_at is not None and time.time() - failed_at > 20.0:      # a rank died: its peers would wait in a collective forever
-            for p in procs:
-                if p.poll() is None:
+            for r, p in enumerate(procs):
+                if r not in ended:
                     p.terminate()                                         # exactly the PIDs started above
             failed_at = time.time() + 1e9
         time.sleep(0.2)
-    for p in procs:
-        if p.returncode != 0 and rc == 0:
-            rc = p.returncode
+    for t in reapers:
+        t.join()
+    failed = sorted(v for v in ended.values() if v[1] != 0)
+    rc = failed[0][1] if failed else 0
     if rc != 0:
         print(f"bench.py launcher: a rank exited with code {rc}", file=sys.stderr)
     return rc if rc > 0 else (1 if rc else 0)
@@ -645,7 +665,15 @@ def main():
                     "graph, the reverse pass continues through the image encoder, AdamW over both parameter buffers")
     ap.add_argument("--train-batch", type=int, default=16, help="train mode: B of the B x B training step (Instructions_*.md: --batch-size 16)")
     ap.add_argument("--index-size", type=int, default=2297, help="bank mode: number of index images (CIRR val: 2297)")
+    ap.add_argument("--full", action="store_true", help="pixels mode: also the side measurements after the timed region - roofline (instrumented step), "
+                    "device clocks / power, rank fidelity against the exact mode, precision table, CPU baseline (the --no-* flags drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="pixels mode: write the last timed step's sorted scores as DIR/<name>.npy "
+                    "(logits float32, indices float64; with N ranks the gathered matrices, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.mode != "pixels":
+        ap.error("--dump-outputs writes the headline path's outputs: pixels mode only")
 
     # the box shows every host core but grants a cgroup quota: the default pool thrashes; N ranks of one node share that quota
     torch.set_num_threads(min(16, max(1, usable_cpus() // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))))
@@ -786,7 +814,7 @@ def main():
         sys.exit(3)                                                     # exchange - its peers block in the collective, the launcher must end them
     exchange()                                                          # warm the communicator too
     fence()
-    with ClockSampler(dev_index) as clocks:
+    with (ClockSampler(dev_index) if args.full else contextlib.nullcontext()) as clocks:
         t0 = time.perf_counter()
         for i in range(args.steps):
             out = step(i)
@@ -819,25 +847,49 @@ def main():
         total_cand = n_cand
     assert torch.isfinite(out).all()
 
-    # ---- instrumented step: HIP events around every GEMM / attention launch on the launch stream ----------------------
-    ops.PROFILE_GEMM, ops.PROFILE_ATTN = [], []
-    step()
-    torch.cuda.synchronize()
-    recs, arecs = ops.PROFILE_GEMM, ops.PROFILE_ATTN
-    ops.PROFILE_GEMM = ops.PROFILE_ATTN = None
-    by_kernel = {}
-    for fl, e0, e1, nbytes, name in recs:
-        d = by_kernel.setdefault(name, dict(flop=0.0, ms=0.0, launches=0, alg_bytes=0.0))
-        d["flop"] += fl; d["ms"] += e0.elapsed_time(e1); d["launches"] += 1; d["alg_bytes"] += nbytes
-    gemm_ms = sum(d["ms"] for d in by_kernel.values())
-    gemm_flop = sum(d["flop"] for d in by_kernel.values())
-    attn_flop = sum(r[0] for r in arecs)
-    attn_ms = sum(r[1].elapsed_time(r[2]) for r in arecs)
-    t1 = time.perf_counter(); step(); torch.cuda.synchronize(); step_ms = (time.perf_counter() - t1) * 1e3
+    # ---- --dump-outputs: what a caller of the path receives from the LAST timed step (rank 0; the gathered matrices with N ranks)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        last = args.steps - 1
+        if use_pg:
+            scores = gathered_scores.view(world, n_buf, q_n, w)[:, last].reshape(world * q_n, w)
+            order = gathered_order.view(world, n_buf, q_n, w)[:, last].reshape(world * q_n, w)
+            queries = order_all
+        else:
+            scores, order, queries = local_scores[last], local_order[last], mine
+        scores, order = scores.cpu().numpy().astype(np.float32), order.cpu().numpy().astype(np.float64)
+        queries = np.asarray(queries, dtype=np.float64)
+        row_bytes = w * (4 + 8) + 8
+        if len(queries) * row_bytes > 64 << 20:                         # a fixed, seeded sample of the queries keeps the dump under 64 MB
+            keep = np.sort(np.random.default_rng(0).choice(len(queries), (64 << 20) // row_bytes, replace=False))
+            scores, order, queries = scores[keep], order[keep], queries[keep]
+        arrays = {"query_index": queries, "topk_logits": scores[:, :k], "topk_order": order[:, :k]}
+        if ns:
+            arrays.update(subset_logits=scores[:, k:], subset_order=order[:, k:])
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a))
+
+    # ---- instrumented step (--full): HIP events around every GEMM / attention launch on the launch stream ---------------
+    if args.full:
+        ops.PROFILE_GEMM, ops.PROFILE_ATTN = [], []
+        step()
+        torch.cuda.synchronize()
+        recs, arecs = ops.PROFILE_GEMM, ops.PROFILE_ATTN
+        ops.PROFILE_GEMM = ops.PROFILE_ATTN = None
+        by_kernel = {}
+        for fl, e0, e1, nbytes, name in recs:
+            d = by_kernel.setdefault(name, dict(flop=0.0, ms=0.0, launches=0, alg_bytes=0.0))
+            d["flop"] += fl; d["ms"] += e0.elapsed_time(e1); d["launches"] += 1; d["alg_bytes"] += nbytes
+        gemm_ms = sum(d["ms"] for d in by_kernel.values())
+        gemm_flop = sum(d["flop"] for d in by_kernel.values())
+        attn_flop = sum(r[0] for r in arecs)
+        attn_ms = sum(r[1].elapsed_time(r[2]) for r in arecs)
+        t1 = time.perf_counter(); step(); torch.cuda.synchronize(); step_ms = (time.perf_counter() - t1) * 1e3
 
     # ---- rank fidelity of THIS run against the exact (fp32) mode on the same step: thousands of sorted positions ---------
     fidelity = None
-    if world == 1 and not args.no_rank_fidelity and args.dtype != "exact":
+    if args.full and world == 1 and not args.no_rank_fidelity and args.dtype != "exact":
         ref_scored = step().clone()
         t32_scored = None
         if args.dtype not in ("text32", "text32x3"):                  # the mode the factories set for real weights, on the same step and referee
@@ -867,7 +919,7 @@ def main():
 
     # ---- the speed / precision trade in the same record: 3 timed steps at each other (operand, stream) precision ---------
     precision = None
-    if world == 1 and not args.no_precision_table and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_precision_table and not args.no_cpu_baseline:
         precision = {f"{args.dtype}+{args.stream_dtype}_stream": round(total_cand * args.steps / elapsed, 1)}
         for od, sd_ in (("f16", "f16"), ("f16", "split"), ("f16", "f32"), ("mixed", "f16"), ("bf16", "f16"), ("bf16", "f32"), ("text32", "split"), ("text32x3", "split")):
             if (od, sd_) == (args.dtype, args.stream_dtype) or (od == args.dtype and od.startswith("text32")):
@@ -900,24 +952,6 @@ def main():
         triplets = total_cand * args.steps
         value = triplets / elapsed
         peak = PEAK_TFLOPS[args.dtype]
-        dom_name = max(by_kernel, key=lambda n: by_kernel[n]["ms"])
-        dom = by_kernel[dom_name]
-        dom_tf = dom["flop"] / (dom["ms"] * 1e-3) / 1e12
-        all_tf = gemm_flop / (gemm_ms * 1e-3) / 1e12
-        # HBM bytes per launch of the dominant kernel: offline PMC passes of this same command (tools/collect_profiles.sh); the
-        # summary names the workload and the hash of the kernel sources it was measured on - any other build reports null
-        traffic, traffic_src = None, None
-        tpath = os.path.join(ROOT, "profiles", "r6_pmc_summary.json")
-        if os.path.exists(tpath):
-            tj = json.load(open(tpath))
-            same = (tj.get("csrc_sha16") == csrc_sha16() and tj.get("queries") == q_n and tj.get("k") == k and tj.get("subset") == ns
-                    and tj.get("image_size") == args.image_size and tj.get("dtype") == args.dtype and args.skip_rate == 0
-                    and tj.get("residual_stream") == args.stream_dtype)
-            ent = tj.get("by_kernel", {}).get(dom_name) if same else None
-            if ent:
-                traffic = round(ent["hbm_bytes_per_launch"])
-                traffic_src = ("profiles/r6_pmc_summary.json: offline rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on these "
-                               "kernel sources (csrc_sha16 matches; not this run)")
         line = {
             "metric": "query-candidate triplets scored/sec at K=100", "value": round(value, 2), "unit": "triplets/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
@@ -930,29 +964,49 @@ def main():
                        "residual_stream": args.stream_dtype,
                        "parallelism": f"queries sharded over {world} GPU(s) (balanced_order blocks), all-gather of scores+indices"},
             "algorithmic_gflop_per_triplet": round(alg_per_triplet, 2),
-            "executed_gflop_per_triplet": round((gemm_flop + attn_flop) / 1e9 / n_cand, 2),
-            "path_tflops": round(value * alg_per_triplet / 1e3, 1),
-            "path_frac_of_mfma_peak": round(value * alg_per_triplet / 1e3 / (peak * world), 4),
-            "roofline": {"bound": "mfma", "kernel": dom_name, "achieved": round(dom_tf, 1), "peak": peak, "unit": "TFLOP/s",
-                         "frac": round(dom_tf / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes": round(dom["alg_bytes"] / dom["launches"]), "launches_per_step": dom["launches"],
-                         "avg_launch_us": round(dom["ms"] * 1e3 / dom["launches"], 2), "share_of_step": round(dom["ms"] / step_ms, 3),
-                         "all_gemm_kernels": {"achieved": round(all_tf, 1), "frac": round(all_tf / peak, 4), "launches_per_step": len(recs),
-                                              "avg_launch_us": round(gemm_ms * 1e3 / max(len(recs), 1), 2), "share_of_step": round(gemm_ms / step_ms, 3),
-                                              "by_kernel": {n: {"tflops": round(d["flop"] / (d["ms"] * 1e-3) / 1e12, 1), "ms_per_step": round(d["ms"], 2),
-                                                                "launches": d["launches"]} for n, d in sorted(by_kernel.items())}},
-                         "attention_kernels": {"tflops": round(attn_flop / (attn_ms * 1e-3) / 1e12, 1), "ms_per_step": round(attn_ms, 2), "launches": len(arecs)},
-                         "peak_definition": ("256 CU x 2.4 GHz x 256 flop/clk/CU f32-input MFMA (MI355X_MICROARCH.md)" if args.dtype == "exact" else
-                                             "256 CU x 2.4 GHz x 4096 flop/clk/CU dense bf16/f16 MFMA (MI355X_MICROARCH.md)")},
-            "device": dict(device_info(), **clocks.summary()),
         }
+        if args.full:
+            line["executed_gflop_per_triplet"] = round((gemm_flop + attn_flop) / 1e9 / n_cand, 2)
+        line["path_tflops"] = round(value * alg_per_triplet / 1e3, 1)
+        line["path_frac_of_mfma_peak"] = round(value * alg_per_triplet / 1e3 / (peak * world), 4)
+        if args.full:
+            dom_name = max(by_kernel, key=lambda n: by_kernel[n]["ms"])
+            dom = by_kernel[dom_name]
+            dom_tf = dom["flop"] / (dom["ms"] * 1e-3) / 1e12
+            all_tf = gemm_flop / (gemm_ms * 1e-3) / 1e12
+            # HBM bytes per launch of the dominant kernel: offline PMC passes of this same command (tools/collect_profiles.sh); the
+            # summary names the workload and the hash of the kernel sources it was measured on - any other build reports null
+            traffic, traffic_src = None, None
+            tpath = os.path.join(ROOT, "profiles", "r6_pmc_summary.json")
+            if os.path.exists(tpath):
+                tj = json.load(open(tpath))
+                same = (tj.get("csrc_sha16") == csrc_sha16() and tj.get("queries") == q_n and tj.get("k") == k and tj.get("subset") == ns
+                        and tj.get("image_size") == args.image_size and tj.get("dtype") == args.dtype and args.skip_rate == 0
+                        and tj.get("residual_stream") == args.stream_dtype)
+                ent = tj.get("by_kernel", {}).get(dom_name) if same else None
+                if ent:
+                    traffic = round(ent["hbm_bytes_per_launch"])
+                    traffic_src = ("profiles/r6_pmc_summary.json: offline rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on these "
+                                   "kernel sources (csrc_sha16 matches; not this run)")
+            line["roofline"] = {"bound": "mfma", "kernel": dom_name, "achieved": round(dom_tf, 1), "peak": peak, "unit": "TFLOP/s",
+                                "frac": round(dom_tf / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
+                                "algorithmic_bytes": round(dom["alg_bytes"] / dom["launches"]), "launches_per_step": dom["launches"],
+                                "avg_launch_us": round(dom["ms"] * 1e3 / dom["launches"], 2), "share_of_step": round(dom["ms"] / step_ms, 3),
+                                "all_gemm_kernels": {"achieved": round(all_tf, 1), "frac": round(all_tf / peak, 4), "launches_per_step": len(recs),
+                                                     "avg_launch_us": round(gemm_ms * 1e3 / max(len(recs), 1), 2), "share_of_step": round(gemm_ms / step_ms, 3),
+                                                     "by_kernel": {n: {"tflops": round(d["flop"] / (d["ms"] * 1e-3) / 1e12, 1), "ms_per_step": round(d["ms"], 2),
+                                                                       "launches": d["launches"]} for n, d in sorted(by_kernel.items())}},
+                                "attention_kernels": {"tflops": round(attn_flop / (attn_ms * 1e-3) / 1e12, 1), "ms_per_step": round(attn_ms, 2), "launches": len(arecs)},
+                                "peak_definition": ("256 CU x 2.4 GHz x 256 flop/clk/CU f32-input MFMA (MI355X peak rate)" if args.dtype == "exact" else
+                                                    "256 CU x 2.4 GHz x 4096 flop/clk/CU dense bf16/f16 MFMA (MI355X peak rate)")}
+            line["device"] = dict(device_info(), **clocks.summary())
         if collective is not None:
             line["collective"] = collective
         if fidelity is not None:
             line["rank_fidelity"] = fidelity
         if precision is not None:
             line["precision_table"] = precision
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(usable_cpus(), k + ns)
         print(json.dumps(line), flush=True)
     if use_pg:

@@ -82,3 +82,28 @@ def test_precision_flags_map_to_model_settings():
     b.apply_precision(m, "f16", "auto")
     assert (m.precision, m.stream_dtype, m.vit_stream_dtype) == ("f16", torch.float16, torch.float16)
     assert set(b.PRECISION_NOTE) == {"f16", "bf16", "mixed", "text32", "text32x3", "exact"} == set(b.PEAK_TFLOPS) and b.PEAK_TFLOPS["exact"] == 157.3
+
+
+def test_cli_rejects_runs_it_cannot_time_or_dump():
+    """Argument checks made before any GPU call: `--steps` is the number of timed steps (at least one), and `--dump-outputs`
+    writes the headline path's outputs (pixels mode only)."""
+    import subprocess
+    import sys
+    for extra, msg in ((["--steps", "0"], "--steps must be >= 1"), (["--mode", "bank", "--dump-outputs", "unused"], "pixels mode only")):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 2 and msg in r.stderr, (r.returncode, r.stderr[-1000:])
+
+
+def test_launcher_reports_the_rank_that_failed_first(tmp_path, monkeypatch):
+    """A rank that dies takes its peers down with it a moment later (their collective fails): the launcher returns the code of the rank
+    that ended first, not that of a peer with a lower rank number whose failure it happened to notice in the same poll."""
+    import sys
+    import time
+    b = _bench()
+    script = tmp_path / "child.py"
+    monkeypatch.setattr(b, "__file__", str(script))
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "4"])
+    for _ in range(3):                                  # rank 1 ends at a common wall-clock time t, the others 50 ms later
+        script.write_text(f"import os, sys, time\nt = {time.time() + 1.5!r}\ntime.sleep(max(0.0, t - time.time()))\n"
+                          "if os.environ['RANK'] == '1':\n    sys.exit(3)\ntime.sleep(0.05)\nsys.exit(1)\n")
+        assert b.launch_ranks(4) == 3

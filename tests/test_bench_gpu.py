@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -23,7 +24,7 @@ def test_single_rank_contract_line():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--queries", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -44,8 +45,36 @@ def test_single_rank_contract_line():
     assert ex["triplets_per_s"] > 100 and 0.3 < ex["gemm_frac_of_f32_mfma_peak"] < 1.0 and ex["f32_mfma_peak_tflops"] == 157.3
 
 
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) does the timed steps and prints the headline only; --dump-outputs writes the last timed step's sorted scores,
+    and a second run with other --steps / --warmup counts (same seeded inputs) writes the same arrays bit for bit."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    runs = []
+    for steps, warmup in ((2, 1), (1, 2)):
+        out = tmp_path / f"s{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--queries", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "triplets/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f16" and d["config"]["triplets_per_step_rank0"] == 2 * 105
+        assert abs(d["value"] - 2 * 105 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+        assert not {"roofline", "device", "rank_fidelity", "precision_table", "cpu_baseline", "executed_gflop_per_triplet"} & set(d)
+        runs.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    a, b = runs
+    assert set(a) == {"query_index", "topk_logits", "topk_order", "subset_logits", "subset_order"} == set(b)
+    assert sum(x.nbytes for x in a.values()) < 64 << 20 and all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert a["topk_logits"].shape == a["topk_order"].shape == (2, 100) and a["subset_logits"].shape == a["subset_order"].shape == (2, 5)
+    for lg, od in ((a["topk_logits"], a["topk_order"]), (a["subset_logits"], a["subset_order"])):
+        assert np.isfinite(lg).all() and (np.sort(od, axis=1) == np.arange(od.shape[1])).all()
+        srt = np.take_along_axis(lg, od.astype(np.int64), axis=1)
+        assert (np.diff(srt, axis=1) <= 0).all()                             # the order sorts the logits, descending
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+
+
 @pytest.mark.parametrize("launcher", ["self", "torchrun"])
-def test_two_rank_dry_run_on_one_gpu(launcher):
+def test_two_rank_dry_run_on_one_gpu(launcher, tmp_path):
     """Both launch forms: `python bench.py --gpus 2` (bench.py starts its own two ranks as child processes before any GPU
     call) and the driver's `python -m torch.distributed.run ... bench.py --gpus 2`."""
     if not torch.cuda.is_available():
@@ -54,7 +83,7 @@ def test_two_rank_dry_run_on_one_gpu(launcher):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--queries", "3", "--skip-rate", "0.34",
-            "--no-precision-table"]
+            "--full", "--no-precision-table", "--dump-outputs", str(tmp_path)]
     if launcher == "self":
         cmd = [sys.executable] + tail
     else:
@@ -70,6 +99,9 @@ def test_two_rank_dry_run_on_one_gpu(launcher):
     assert r.stdout.count('{"metric"') == 1          # rank 0 alone prints the line
     c = d["collective"]
     assert c["ranks"] == 2 and c["own_block_bit_identical"] and c["checksum_equal_on_all_ranks"] and len(c["per_rank_triplets_per_step"]) == 2
+    # --dump-outputs: rank 0 writes the gathered matrices, one row per query of both ranks (rows in balanced_order)
+    qi, lg, od = (np.load(tmp_path / f"{n}.npy") for n in ("query_index", "topk_logits", "topk_order"))
+    assert sorted(qi.tolist()) == list(range(6)) and lg.shape == od.shape == (6, 100) and np.load(tmp_path / "subset_logits.npy").shape == (6, 5)
 
 
 def test_eight_rank_dry_run_and_a_dying_rank():
@@ -84,7 +116,7 @@ def test_eight_rank_dry_run_and_a_dying_rank():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--queries", "2", "--skip-rate", "0.2",
-           "--no-precision-table"]
+           "--full", "--no-precision-table"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
@@ -94,7 +126,7 @@ def test_eight_rank_dry_run_and_a_dying_rank():
     assert sum(c["per_rank_triplets_per_step"]) > 0 and max(c["per_rank_triplets_per_step"]) - min(c["per_rank_triplets_per_step"]) <= 100   # balanced_order: blocks differ by <= 1 scored query
     assert "rank_fidelity" not in d and "cpu_baseline" not in d                 # single-rank blocks only
     t0 = time.time()
-    cmd2 = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "1", "--queries", "2", "--no-precision-table"]
+    cmd2 = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "1", "--warmup", "1", "--queries", "2", "--full", "--no-precision-table"]
     r = subprocess.run(cmd2, capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(env, CIR_BENCH_FAIL_RANK="1"))
     assert r.returncode != 0 and '{"metric"' not in r.stdout and "a rank exited with code 3" in r.stderr, (r.returncode, r.stderr[-1500:])
     print(f"\n[dying rank] launcher returned {r.returncode} after {time.time() - t0:.0f} s")
@@ -119,7 +151,7 @@ def test_one_rank_rccl_exchange_runs_on_device_tensors():
     env = dict(os.environ, CIR_BENCH_INIT_PG="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--queries", "2",
-                        "--skip-rate", "0.5", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        "--skip-rate", "0.5", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _last_json(r.stdout)
     c = d["collective"]
@@ -165,13 +197,14 @@ def test_text32_and_latency_lines():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dtype", "text32", "--steps", "1", "--warmup", "1", "--queries", "2",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert d["dtype"] == "text32" and d["value"] > 0 and d["config"]["residual_stream"] == "split" and "split8" in d["config"]["precision_mode"]
     assert d["rank_fidelity"]["kendall_tau"] > 0.99 and d["rank_fidelity"]["max_abs_dlogit"] < 2e-3 and "text32" not in d["rank_fidelity"]     # (no sub-block of itself)
     # the default mode's line carries the real-weights mode twice: its order against the exact referee, and its throughput at the headline's step count
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--queries", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--queries", "2", "--full"], capture_output=True, text=True,
+                       timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     t32 = d["rank_fidelity"]["text32"]

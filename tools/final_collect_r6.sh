@@ -6,7 +6,7 @@ python bench.py --mode train --image-size 384 --dtype bf16 --steps 10 --warmup 3
 python bench.py --mode train --image-size 384 --img-tune --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_train_mode_img_tune.json 2>> $O/err.txt
 python bench.py --mode train --image-size 224 --train-batch 32 --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_train_mode_b32_224.json 2>> $O/err.txt
 python bench.py --mode loop --dtype text32 --loop-queries 4181 --query-batch 64 > $O/bench_loop_cirr_val_4181_text32.json 2>> $O/err.txt
-python bench.py --steps 20 --warmup 5 > $O/bench_default_20steps_final.json 2>> $O/err.txt
+python bench.py --full --steps 20 --warmup 5 > $O/bench_default_20steps_final.json 2>> $O/err.txt
 for f in $O/bench_*.json gpurun_out/r6_stats.json gpurun_out/r6_text32_stats.json; do python - "$f" <<'PY'
 import json, sys
 try:

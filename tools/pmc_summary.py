@@ -111,7 +111,7 @@ def main():
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
     res = {**meta, "csrc_sha16": bench.csrc_sha16(),
-           "source": "rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-precision-table "
+           "source": "rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-precision-table "
                      "(one pass per counter group; all launches of the run incl. warm-up and the instrumented steps)",
            "passes": passes, "by_kernel": {}}
     for k, e in sorted(ker.items()):
