@@ -41,6 +41,9 @@ class BLIP_Retrieval(_EngineHost):
         self.text_encoder.config = self.bert_geometry
 
     def engines(self):
+        key = self.weights_key()
+        if self._engines is not None and key != self._packed_key:            # a parameter was written since the pack (`weights_key`)
+            self._engines = None
         if self._engines is None:
             dev = self.device
             if dev.type != "cuda":
@@ -51,6 +54,7 @@ class BLIP_Retrieval(_EngineHost):
                                        split3=self.text_split3 if self.precision == "text32" else 0),
                              VitEngine(sd, self.vit_geometry, self.token_dtype, dev, stream_dtype=self.vit_stream_dtype),
                              dict(vw=f32("vision_proj.weight"), vb=f32("vision_proj.bias"), tw=f32("text_proj.weight"), tb=f32("text_proj.bias")))
+            self._packed_key = key
         return self._engines
 
     @torch.no_grad()

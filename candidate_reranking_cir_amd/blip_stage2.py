@@ -12,11 +12,14 @@ stream).  Inference only: no autograd graph is built.
 """
 from __future__ import annotations
 
+import operator
 import os
 from typing import Optional, Sequence, Union
 
 import torch
 from torch import nn
+from torch.autograd.graph import increment_version
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import lib as _lib
 from . import ops
@@ -71,14 +74,38 @@ def encode_text(tokenizer, text, device):
     return ids, mask.to(device=device, dtype=torch.int64)
 
 
+_VERSION = operator.attrgetter("_version")
+
+
+def _on_optimizer_step(optimizer, args, kwargs):
+    """Post-hook of every torch.optim step (foreach / fused kernels and GradScaler.step included): whatever the optimizer's kernels
+    did to the parameters' version counters, the parameters it holds count as written - the packed copies compare those counters."""
+    increment_version([p for group in optimizer.param_groups for p in group["params"]])
+    _lib.PARAM_EPOCH[0] += 1
+
+
+register_optimizer_step_post_hook(_on_optimizer_step)
+
+_LOAD_EPOCH = [0]      # moved by every load_state_dict of a model or of one of its submodules (post-hook; module-level so that models pickle)
+
+
+def _on_load_state_dict(module, incompatible_keys):
+    """load_state_dict(assign=True) replaces Parameter objects, whose version counters start afresh: keys and parameter lists move."""
+    _LOAD_EPOCH[0] += 1
+
+
 class _EngineHost(nn.Module):
-    """Shared plumbing: lazily packed engines, invalidated when parameters move or are reloaded."""
+    """Shared plumbing: lazily packed engines, repacked when the parameters they were packed from are written (`weights_key`)."""
+
+    _PARTS = {"text": ("text_encoder.", "cls_head."), "vit": ("visual_encoder.",)}
 
     def __init__(self):
         super().__init__()
         self._engines = None
-        self._packed_epoch = 0
-        self._text_stale = False               # set by a training step (train.py): text_encoder / cls_head changed, the ViT did not
+        self._weights_epoch = 0                # moved by `invalidate_packed_weights`
+        self._param_lists = None               # part -> the parameters `weights_key` reads (cached; rebuilt after a load_state_dict)
+        self._lists_epoch = -1
+        self._loads_hooked = False
         self.compute_dtype = torch.float16     # operand type of the text side (self-attention, FFN, cls_head); fp16 holds the
                                                # reference's rank order where bf16 does not (DESIGN.md section 2) - `set_precision`
         self.image_dtype = None                # operand type of the ViT and the cross-attention block (None: = compute_dtype)
@@ -205,11 +232,42 @@ class _EngineHost(nn.Module):
 
     def _apply(self, fn, *a, **k):
         self._engines = None
+        self.invalidate_packed_weights()
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
         self._engines = None
         return super().load_state_dict(*a, **k)
+
+    # ---------------------------------------------------------------------------------------------- packed-weight coherence
+    def invalidate_packed_weights(self):
+        """Every packed copy of the parameters - inference engines with their captured graphs and K/V banks, the trainers' 16-bit
+        slabs - is rebuilt on its next use.  Needed after writes no version counter sees: `p.data.copy_(...)`, `p.data = ...` of a
+        single submodule, a raw kernel on the parameters' memory.  In-place torch ops on the parameters, torch.optim steps,
+        `train.AdamW.step` and `load_state_dict` of the model or any submodule are followed without it."""
+        self._weights_epoch += 1
+        self._param_lists = None
+        return self
+
+    def _part_params(self, part: str):
+        if not self._loads_hooked:                 # load_state_dict(assign=True) of a submodule replaces Parameter objects: new list
+            for mod in self.modules():
+                mod.register_load_state_dict_post_hook(_on_load_state_dict)
+            self._loads_hooked = True
+        if self._param_lists is None or self._lists_epoch != _LOAD_EPOCH[0]:
+            self._param_lists, self._lists_epoch = {}, _LOAD_EPOCH[0]
+        ps = self._param_lists.get(part)
+        if ps is None:
+            pre = self._PARTS.get(part)
+            ps = self._param_lists[part] = [p for n, p in self.named_parameters() if pre is None or n.startswith(pre)]
+        return ps
+
+    def weights_key(self, part: str = "all") -> tuple:
+        """Staleness key of the parameters of `part` ("text": text_encoder + cls_head, "vit": visual_encoder, "all"): what a packed copy
+        records when it is written and compares before it is used.  (epoch, sum of the parameters' version counters): every in-place
+        torch op moves a counter, torch.optim steps and train.AdamW.step move them explicitly (their kernels write through pointers)."""
+        ps = self._part_params(part)
+        return (self._weights_epoch, _LOAD_EPOCH[0], sum(map(_VERSION, ps)))
 
     @property
     def device(self):
@@ -232,35 +290,35 @@ class BLIP_NLVR(_EngineHost):
         self.text_encoder.config = self.bert_geometry                        # callers read .config.hidden_size
 
     # ------------------------------------------------------------------------------------------
-    def engines(self, text: bool = True):
+    def _text_engine(self, sd) -> NlvrEngine:
+        e = NlvrEngine(sd, self.bert_geometry, self.compute_dtype, self.device, fold_merge=self.fold_merge and self.compute_dtype != torch.float32,
+                       stream_dtype=self.stream_dtype, cross_dtype=self.token_dtype, split3=self.text_split3 if self.precision == "text32" else 0)
+        e.stream32_from = self.text_stream32_from
+        return e
+
+    def _vit_engine(self, sd) -> VitEngine:
+        return VitEngine(sd, self.vit_geometry, self.token_dtype, self.device, stream_dtype=self.vit_stream_dtype)
+
+    def engines(self, text: bool = True, vit: bool = True):
+        """(VitEngine, NlvrEngine) packed from the parameters.  A part whose `weights_key` moved since it was packed is repacked before it
+        is returned - the text side when `text`, the ViT when `vit` (callers that use one engine only skip the other's check)."""
         if self._engines is None:
-            dev = self.device
-            if dev.type != "cuda":
+            if self.device.type != "cuda":
                 raise RuntimeError("BLIP_NLVR runs on an MI355X only: move the model to 'cuda' (no CPU path)")
+            self._packed_keys = [self.weights_key("vit"), self.weights_key("text")]
             sd = self.state_dict()
-            self._engines = (VitEngine(sd, self.vit_geometry, self.token_dtype, dev, stream_dtype=self.vit_stream_dtype),
-                             NlvrEngine(sd, self.bert_geometry, self.compute_dtype, dev, fold_merge=self.fold_merge and self.compute_dtype != torch.float32, stream_dtype=self.stream_dtype,
-                                        cross_dtype=self.token_dtype, split3=self.text_split3 if self.precision == "text32" else 0))
-            self._engines[1].stream32_from = self.text_stream32_from
-            self._text_stale = False
-            self._packed_epoch = _lib.PARAM_EPOCH[0]
-            self._vit_stale = False                    # (a full build packs the ViT too: no second VitEngine below - round-4 advisor finding)
-            self._vit_packed_epoch = _lib.PARAM_EPOCH[0]
-        if self._engines is not None and (getattr(self, "_vit_stale", False) or (getattr(self, "_vit_trainer", None) is not None
-                                                                                 and getattr(self, "_vit_packed_epoch", None) != _lib.PARAM_EPOCH[0])):
-            # the ViT is being fine-tuned (train_vit.py): its packed engine follows the parameters the same way the text side's does
-            self._engines = (VitEngine(self.state_dict(), self.vit_geometry, self.token_dtype, self.device, stream_dtype=self.vit_stream_dtype),
-                             self._engines[1])
-            self._vit_stale = False
-            self._vit_packed_epoch = _lib.PARAM_EPOCH[0]
-        if text and self._engines is not None and (self._text_stale or (getattr(self, "_trainer", None) is not None and self._packed_epoch != _lib.PARAM_EPOCH[0])):
-            # after training steps (the forward marks it; every cir_adamw_step launch moves lib.PARAM_EPOCH, so an eval call made
-            # between backward() and step() cannot leave the engine on the pre-step weights): repack the two-branch encoder only (the ViT is frozen there),
-            self._engines = (self._engines[0], NlvrEngine(self.state_dict(), self.bert_geometry, self.compute_dtype, self.device,
-                                                          fold_merge=self.fold_merge and self.compute_dtype != torch.float32, stream_dtype=self.stream_dtype, cross_dtype=self.token_dtype, split3=self.text_split3 if self.precision == "text32" else 0))
-            self._engines[1].stream32_from = self.text_stream32_from
-            self._text_stale = False           # and only when a caller needs it (`text`): img_embed between steps does not
-            self._packed_epoch = _lib.PARAM_EPOCH[0]
+            self._engines = (self._vit_engine(sd), self._text_engine(sd))
+            return self._engines
+        if vit:
+            k = self.weights_key("vit")
+            if k != self._packed_keys[0]:
+                self._packed_keys[0] = k
+                self._engines = (self._vit_engine(self.state_dict()), self._engines[1])
+        if text:
+            k = self.weights_key("text")
+            if k != self._packed_keys[1]:
+                self._packed_keys[1] = k
+                self._engines = (self._engines[0], self._text_engine(self.state_dict()))
         return self._engines
 
     def img_embed(self, image, train=True, atts=False):
@@ -310,7 +368,7 @@ class BLIP_NLVR(_EngineHost):
         """Batched scoring: z_t (Q,L,D), ids/mask (Q,L) with [ENC] already set, cand (T,N,D),
         qidx (T,) -> (T,) fp32 logits (column 0 of cls_head).  `kv_bank` + `cand_rows` score candidates
         straight out of a per-image cross-attention K/V bank (`build_kv_bank`)."""
-        eng = self.engines()[1]
+        eng = self.engines(vit=False)[1]
         if self.graph_candidates and kv_bank is None and taps is None and cand.shape[0] <= self.graph_candidates:
             # small problems are bound by launch issue from the host: one captured HIP graph per shape (engine.ScoreGraph)
             return eng.forward_graphed(input_ids.to(self.device), attention_mask.to(self.device), z_t.to(self.device), self._cand16(cand),
@@ -323,7 +381,7 @@ class BLIP_NLVR(_EngineHost):
     @torch.no_grad()
     def build_kv_bank(self, bank: torch.Tensor) -> list:
         """Per-image, per-layer cross-attention K|V of an index-feature bank (n_index, N, D)."""
-        return self.engines()[1].build_kv_bank(self._cand16(bank))
+        return self.engines(vit=False)[1].build_kv_bank(self._cand16(bank))
 
     @torch.no_grad()
     def img_txt_fusion_val(self, r_image_embeds, t_image_embeds, text):

@@ -20,6 +20,7 @@ nlvr_encoder.py:414-476 / 777-908, blip_stage2.py:101-136.
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, Optional
 
 import torch
@@ -220,8 +221,11 @@ class VitEngine:
 class KVBank(list):
     """Per-layer cross-attention K|V of an index-feature bank: entry i is (n_index, N, 4D) - or None for
     the last layer when its K / V projections are folded out of the token side, which then reads `tokens` (the 16-bit
-    index features themselves) through cir_cls_cross_attention's row index."""
+    index features themselves) through cir_cls_cross_attention's row index.  `engine`: weak reference to the NlvrEngine that built it -
+    a bank holds projections of that engine's weights, and `NlvrEngine.forward` refuses it from any other (a repacked engine: the
+    parameters were written since the bank was built)."""
     tokens: Optional[torch.Tensor] = None
+    engine = None
 
 
 def _cat(sd: SD, keys, suffix: str) -> torch.Tensor:
@@ -430,6 +434,7 @@ class NlvrEngine:
         d = self.geo.hidden_size
         out = KVBank()
         out.tokens = bank16
+        out.engine = weakref.ref(self)
         last = len(self.layers) - 1
         for i, ly in enumerate(self.layers):
             if i == last and self.trim_last and last > 0 and self.cls_fold is not None and self.fold_cls_kv:
@@ -476,6 +481,9 @@ class NlvrEngine:
         sdt = sd(0)
         q_n, l = input_ids.shape
         if kv_bank is not None:
+            if getattr(kv_bank, "engine", None) is None or kv_bank.engine() is not self:
+                raise RuntimeError("kv_bank was not built by this engine: the model's parameters were written (or its precision changed) since "
+                                   "build_kv_bank - its K/V are projections of the old weights; build the bank again")
             cand_rows = cand_rows.to(torch.int64).contiguous()
             t_n, n = cand_rows.shape[0], kv_bank[0].shape[1]
         else:

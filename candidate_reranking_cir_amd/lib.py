@@ -93,7 +93,7 @@ SIGNATURES = {
 }
 
 _lib = None
-PARAM_EPOCH = [0]     # moved by every cir_adamw_step launch (train_ops.adamw_step): packed inference engines of a trained model compare it
+PARAM_EPOCH = [0]     # moved by every cir_adamw_step launch and torch.optim step: a ViT training forward's backward compares it (train_vit.py)
 
 
 class CirrankError(RuntimeError):

@@ -30,11 +30,12 @@ from __future__ import annotations
 
 import math
 import weakref
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, Optional
 
 import torch
+from torch.autograd.graph import increment_version
 
-from . import lib, ops, train_ops as T
+from . import ops, train_ops as T
 
 
 def _cast(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
@@ -63,12 +64,13 @@ _SLABS: Dict[int, "weakref.ref"] = {}     # flat32 base pointer -> the slab that
 
 class _Slab:
     """The trained parameters as ONE flat fp32 buffer (each nn.Parameter's `.data` re-pointed to its slice: optimizers update the
-    buffer in place), their 16-bit operand copies as one flat buffer refreshed by one cast per step, and their gradients as one
-    flat fp32 buffer zeroed once per step - three launches where per-tensor copies took ~900.  Slices start at multiples of 8
-    elements (16-byte rows for the 16-bit views)."""
+    buffer in place), their 16-bit operand copies as one flat buffer refreshed by one cast when the parameters were written, and their
+    gradients as one flat fp32 buffer zeroed once per step - three launches where per-tensor copies took ~900.  Slices start at multiples
+    of 8 elements (16-byte rows for the 16-bit views).  `key`: the model's staleness key of these parameters (`_EngineHost.weights_key`):
+    each Parameter keeps its own version counter after `p.data = view`, so the flat buffer's own counter sees none of their writes."""
 
-    def __init__(self, params: Dict[str, torch.nn.Parameter], names: List[str], dtype: torch.dtype):
-        self.params, self.names, self.dtype = params, names, dtype
+    def __init__(self, params: Dict[str, torch.nn.Parameter], names: List[str], dtype: torch.dtype, key: Callable[[], tuple]):
+        self.params, self.names, self.dtype, self.key = params, names, dtype, key
         self.off, o = {}, 0
         for n in names:
             self.off[n] = o
@@ -84,7 +86,7 @@ class _Slab:
         _SLABS[self.flat32.data_ptr()] = weakref.ref(self)
         self.flat16 = self.flat16t = self.gflat = self.plan = None
         self.checked = None                                                         # (gradient buffer pointer, its "all finite" device flag)
-        self._fresh16 = None                                                        # (flat32._version, PARAM_EPOCH) flat16 was written for
+        self._fresh16 = None                                                        # the `key` flat16 was written for
 
     def _view(self, flat: torch.Tensor, n: str) -> torch.Tensor:
         p = self.params[n]
@@ -95,21 +97,24 @@ class _Slab:
         return all(self.params[n].data_ptr() == base + 4 * self.off[n] for n in self.names)
 
     def begin_step(self):
-        """One cast launch refreshes the persistent 16-bit copy, one multi-transpose launch the dgrad operands (`plan`, built by the
-        trainer from its dense layers), one fill the fresh gradient buffer."""
+        """One cast launch refreshes the persistent 16-bit copy (when the parameters were written since it was), one multi-transpose launch
+        the dgrad operands (`plan`, built by the trainer from its dense layers), one fill the fresh gradient buffer."""
         if self.flat16 is None:
             self.flat16 = torch.empty(self.flat32.shape, dtype=self.dtype, device=self.flat32.device)
             self.flat16t = torch.zeros_like(self.flat16)
-        if self._fresh16 != (self.flat32._version, lib.PARAM_EPOCH[0]):             # (AdamW.step below writes flat16 in its own pass)
+        key = self.key()
+        if self._fresh16 != key:                                                    # (AdamW.step below writes flat16 in its own pass)
             T.eltwise(self.flat32, T.MODE_SCALE, p_drop=1.0, out=self.flat16)
+            self._fresh16 = key
         if self.plan is not None:
             self.plan.run(self.flat16, self.flat16t)
         self.gflat = torch.zeros_like(self.flat32)
 
     def mark_fresh16(self):
-        """flat16 holds the 16-bit copy of flat32 AS IT IS NOW (the optimizer wrote both): the next begin_step skips its cast unless a torch
-        op (another optimizer, a manual edit: the version counter moves) or another of our launches (PARAM_EPOCH) touches the parameters first."""
-        self._fresh16 = (self.flat32._version, lib.PARAM_EPOCH[0])
+        """flat16 holds the 16-bit copy of flat32 AS IT IS NOW (the optimizer wrote both; called once the step has moved the key): the next
+        begin_step skips its cast unless the parameters are written first (an in-place torch op, torch.optim, load_state_dict,
+        `invalidate_packed_weights`)."""
+        self._fresh16 = self.key()
 
     def w32(self, n): return self._view(self.flat32, n)
     def w16(self, n): return self._view(self.flat16, n)
@@ -380,7 +385,7 @@ class NlvrTrainer:
         slab = getattr(self, "slab", None)
         if slab is None or slab.dtype != self.dtype or not slab.valid():           # first step, or the model was moved / re-cast
             P = dict(self.model.named_parameters())
-            slab = self.slab = _Slab(P, self._order([n for n in P if self._trained(n)]), self.dtype)
+            slab = self.slab = _Slab(P, self._order([n for n in P if self._trained(n)]), self.dtype, key=lambda: self.model.weights_key("text"))
             slab.begin_step()                                                       # allocates the 16-bit buffers the views below slice
             self._build_layers(slab)
         slab.begin_step()
@@ -460,8 +465,7 @@ class NlvrTrainer:
     def forward(self, z_t: torch.Tensor, feats: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         """z_t (B, L, D) fp32, feats (B, N, Dv), ids / mask (B, L) with [ENC] set -> logits (B, B) fp32; keeps what backward needs."""
         self._pack()
-        self.model._text_stale = True                                               # a training step is about to change text_encoder / cls_head:
-        self.step_no += 1                                                           # the inference engine of that part repacks on its next use
+        self.step_no += 1
         g, dt, dev = self.geo, self.dtype, z_t.device
         b_n, l = input_ids.shape
         n, d = feats.shape[1], g.hidden_size
@@ -748,8 +752,8 @@ class AdamW:
     updates all of them; otherwise one launch per tensor."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None, check_finite=None):
-        """`model`: the BLIP_NLVR whose parameters these are - its packed inference engine is marked stale by every step()
-        (without it the training forward marks it, which misses an eval call made between backward() and step()).
+        """`model`: the BLIP_NLVR whose parameters these are (its trainers' finite flags decide the skip; every step() moves the
+        parameters' version counters, which the packed inference engines and the 16-bit slabs compare, with or without it).
         `check_finite`: test the gradients step() is about to apply for inf / NaN and skip the update then (GradScaler.step's found_inf,
         stage2_train.py:215-218; one reduction over the flat gradient buffer + one host read).  None = automatic: always, unless `model`
         is given and its trainers run bf16 operands (whose pass cannot overflow: no loss scale)."""
@@ -891,12 +895,13 @@ class AdamW:
             T.adamw_step_dev(pf, gf_, m, v, st, self.lr, self.betas, self.eps, self.wd, p16=p16)
             if back is not None:                              # (a non-contiguous parameter stepped through a contiguous copy)
                 back.data.copy_(pf)
-            if slab is not None:
-                slab.mark_fresh16()                           # (a skipped step leaves both copies as they were: still consistent)
-        if self.model is not None:
-            self.model._text_stale = True                     # the weights change HERE: the next eval / score call repacks
-            if getattr(self.model, "_vit_trainer", None) is not None:
-                self.model._vit_stale = True
+        # the kernels wrote through pointers: move the parameters' version counters, which the packed copies (engines, graphs, K/V banks,
+        # slabs) compare - then the slabs whose 16-bit copy was written along record the key as it now is (all of them: a slab marked before
+        # a later launch of this step would re-cast at its next step)
+        increment_version(ps)
+        for w in work:
+            if w[5] is not None:
+                w[5].mark_fresh16()                           # (a skipped step leaves both copies as they were: still consistent)
 
     def zero_grad(self):
         for p in self.params:

@@ -58,7 +58,7 @@ class VitTrainer:
         slab = getattr(self, "slab", None)
         if slab is None or slab.dtype != self.dtype or not slab.valid():
             P = {n: p for n, p in self.model.named_parameters() if self._trained(n)}
-            slab = self.slab = _Slab(P, list(P), self.dtype)
+            slab = self.slab = _Slab(P, list(P), self.dtype, key=lambda: self.model.weights_key("vit"))
             slab.begin_step()
             lins: List[_Lin] = []
 
@@ -92,7 +92,6 @@ class VitTrainer:
     def forward(self, image: torch.Tensor) -> torch.Tensor:
         """(B, 3, H, W) -> (B, N, D) fp32 image tokens (VisionTransformer.forward, vit.py:180-194); keeps what backward needs."""
         self._pack()
-        self.model._vit_stale = True
         geo, dt = self.geo, self.dtype
         if image.shape[-1] != geo.image_size or image.shape[-2] != geo.image_size:
             raise ValueError(f"image size {tuple(image.shape[-2:])} != model image_size {geo.image_size}")
