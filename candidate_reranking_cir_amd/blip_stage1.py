@@ -53,7 +53,8 @@ class BLIP_Retrieval(_EngineHost):
             self._engines = (MedEngine(sd, self.bert_geometry, self.compute_dtype, dev, stream_dtype=self.stream_dtype, cross_dtype=self.token_dtype,
                                        split3=self.text_split3 if self.precision == "text32" else 0),
                              VitEngine(sd, self.vit_geometry, self.token_dtype, dev, stream_dtype=self.vit_stream_dtype),
-                             dict(vw=f32("vision_proj.weight"), vb=f32("vision_proj.bias"), tw=f32("text_proj.weight"), tb=f32("text_proj.bias")))
+                             dict(vw=f32("vision_proj.weight"), vb=f32("vision_proj.bias"), tw=f32("text_proj.weight"), tb=f32("text_proj.bias"),
+                                  temp=f32("temp").reshape(1)))
             self._packed_key = key
         return self._engines
 
@@ -103,18 +104,31 @@ class BLIP_Retrieval(_EngineHost):
             cur = self._med_dropout = (self._engines, MedDropoutForward(eng, ph, pa))
         return cur[1]
 
-    @torch.no_grad()
     def img_txt_fusion(self, r_image_embeds, t_image_embeds, text, train=True, return_raw=False):
-        """blip_stage1.py:67-92 in eval mode: `return_raw` -> z_t object (stage-II input); otherwise the normalised
-        256-d query feature `F.normalize(text_proj(z_t[:, 0]))` used by stage-I retrieval."""
-        if train:
-            raise NotImplementedError("forward only: the contrastive training branch (blip_stage1.py:88-92) is out of scope")
-        ids, mask = encode_text(self.tokenizer, text, self.device)          # blip_stage1.py:72-73
-        z = self.z_t(r_image_embeds, ids, mask)
-        if return_raw:
-            return z
-        heads = self.engines()[2]
-        return ops.l2_normalize(ops.linear_f32(z.last_hidden_state[:, 0, :], heads["tw"], heads["tb"]))
+        """blip_stage1.py:67-92.  train=False: `return_raw` -> z_t object (stage-II input); otherwise the normalised 256-d query feature
+        `F.normalize(text_proj(z_t[:, 0]))` used by stage-I retrieval.  train=True: logits = that feature @ t_image_embeds^T / temp (B, Bt),
+        t_image_embeds the normalised pooled target features (B, 256).  In .train() mode with grad enabled that is the stage-I training step
+        (stage1_train.py:170-172): the logits are differentiable w.r.t. the encoder layers, embeddings, text_proj and temp
+        (train_stage1.MedTrainer); in .eval() mode or under no_grad the same head runs on this mode's z_t, without a graph."""
+        if not train:
+            with torch.no_grad():
+                ids, mask = encode_text(self.tokenizer, text, self.device)          # blip_stage1.py:72-73
+                z = self.z_t(r_image_embeds, ids, mask)
+                if return_raw:
+                    return z
+                heads = self.engines()[2]
+                return ops.l2_normalize(ops.linear_f32(z.last_hidden_state[:, 0, :], heads["tw"], heads["tb"]))
+        from . import train_ops as T
+        from .train_stage1 import _refuse_image_grads, stage1_train
+        _refuse_image_grads(r_image_embeds, t_image_embeds)
+        ids, mask = encode_text(self.tokenizer, text, self.device)
+        if self.training and torch.is_grad_enabled():
+            return stage1_train(self, r_image_embeds, t_image_embeds, ids, mask)
+        with torch.no_grad():
+            z = self.z_t(r_image_embeds, ids, mask)
+            heads = self.engines()[2]
+            p = ops.linear_f32(z.last_hidden_state[:, 0, :], heads["tw"], heads["tb"])
+            return T.contrastive_fwd(p, t_image_embeds.to(self.device).float().contiguous(), heads["temp"])[2]
 
 
 def blip_stage1(pretrained: str = "", **kwargs) -> BLIP_Retrieval:

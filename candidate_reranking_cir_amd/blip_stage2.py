@@ -97,7 +97,8 @@ def _on_load_state_dict(module, incompatible_keys):
 class _EngineHost(nn.Module):
     """Shared plumbing: lazily packed engines, repacked when the parameters they were packed from are written (`weights_key`)."""
 
-    _PARTS = {"text": ("text_encoder.", "cls_head."), "vit": ("visual_encoder.",)}
+    _PARTS = {"text": ("text_encoder.", "cls_head."), "vit": ("visual_encoder.",),
+              "stage1_train": ("text_encoder.", "text_proj.", "temp")}          # what the stage-I trainer's slab holds (train_stage1.py)
 
     def __init__(self):
         super().__init__()

@@ -679,6 +679,132 @@ __global__ __launch_bounds__(256) void adamw_dev_kernel(float* p, const float* g
     }
 }
 
+// ---- contrastive head of the stage-I training step (blip_stage1.py:83-91): p_hat = F.normalize(p), logits = p_hat target^T / temp, and its
+// adjoint.  ~0.5 GFLOP at B = 1024: plain fp32 FMA chains, every reduction in a fixed order (wave butterflies, block trees, serial loops over
+// rows) and no atomics - the head's outputs repeat bit for bit.  temp is read on the device.
+constexpr int kHeadMaxE = 1024;
+
+// fixed-order sum over a 256-thread block (wave butterflies, then the four wave sums in order); every thread gets the result
+__device__ __forceinline__ float block256_sum(float v, float* red4) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red4[0] + red4[1]) + red4[2]) + red4[3];
+}
+
+// one block per query row i: its norm, p_hat row and inverse norm, then one wave per target column j
+__global__ __launch_bounds__(256) void contrastive_fwd_kernel(const float* __restrict__ p, const float* __restrict__ target,
+                                                              const float* __restrict__ temp, float* __restrict__ p_hat,
+                                                              float* __restrict__ inv_norm, float* __restrict__ logits, int Bt, int E) {
+    __shared__ float ph[kHeadMaxE];
+    __shared__ float red4[4];
+    const int64_t i = blockIdx.x;
+    const int t = threadIdx.x;
+    const float* pr = p + i * E;
+    float s = 0.f;
+    for (int e = t; e < E; e += 256) s = fmaf(pr[e], pr[e], s);
+    const float nrm = fmaxf(sqrtf(block256_sum(s, red4)), 1e-12f);      // F.normalize: x / max(||x||, eps)
+    for (int e = t; e < E; e += 256) {
+        const float v = pr[e] / nrm;
+        ph[e] = v;
+        p_hat[i * E + e] = v;
+    }
+    if (t == 0) inv_norm[i] = 1.f / nrm;
+    __syncthreads();
+    const float tp = temp[0];
+    const int wave = t >> 6, lane = t & 63;
+    for (int j = wave; j < Bt; j += 4) {
+        const float* tr = target + (int64_t)j * E;
+        float acc = 0.f;
+        for (int e = lane; e < E; e += 64) acc = fmaf(ph[e], tr[e], acc);
+        acc = wave_sum(acc);
+        if (lane == 0) logits[i * Bt + j] = acc / tp;
+    }
+}
+
+// adjoint, one block per query row i: dp_hat = dlogits[i] . target / temp, dp = (dp_hat - p_hat (p_hat . dp_hat)) / ||p||; the row's
+// p_hat . dp_hat = sum_j dlogits_ij logits_ij is kept for dtemp
+__global__ __launch_bounds__(256) void contrastive_bwd_rows_kernel(const float* __restrict__ dlogits, const float* __restrict__ target,
+                                                                   const float* __restrict__ temp, const float* __restrict__ p_hat,
+                                                                   const float* __restrict__ inv_norm, float* __restrict__ dp,
+                                                                   float* __restrict__ row_dot, int Bt, int E) {
+    __shared__ float red4[4];
+    const int64_t i = blockIdx.x;
+    const int t = threadIdx.x;
+    const float* dl = dlogits + i * Bt;
+    float acc[kHeadMaxE / 256];
+#pragma unroll
+    for (int c = 0; c < kHeadMaxE / 256; ++c) acc[c] = 0.f;
+    for (int j = 0; j < Bt; ++j) {
+        const float g = dl[j];
+        const float* tr = target + (int64_t)j * E;
+#pragma unroll
+        for (int c = 0; c < kHeadMaxE / 256; ++c) {
+            const int e = t + 256 * c;
+            if (e < E) acc[c] = fmaf(g, tr[e], acc[c]);
+        }
+    }
+    const float tp = temp[0];
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < kHeadMaxE / 256; ++c) {
+        const int e = t + 256 * c;
+        if (e < E) {
+            acc[c] /= tp;
+            s = fmaf(p_hat[i * E + e], acc[c], s);
+        }
+    }
+    const float sd = block256_sum(s, red4);
+    const float inv = inv_norm[i];
+#pragma unroll
+    for (int c = 0; c < kHeadMaxE / 256; ++c) {
+        const int e = t + 256 * c;
+        if (e < E) dp[i * E + e] = (acc[c] - p_hat[i * E + e] * sd) * inv;
+    }
+    if (t == 0) row_dot[i] = sd;
+}
+
+// text_proj dgrad: dx[i][d] = sum_e dp[i][e] W[e][d]  (written into rows of stride lddx: the CLS rows of the stream gradient)
+__global__ __launch_bounds__(256) void head_dgrad_kernel(const float* __restrict__ dp, const float* __restrict__ W, float* __restrict__ dx,
+                                                         int64_t lddx, int E, int D) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    const int64_t i = blockIdx.y;
+    if (d >= D) return;
+    const float* g = dp + i * E;
+    float acc = 0.f;
+    for (int e = 0; e < E; ++e) acc = fmaf(g[e], W[(int64_t)e * D + d], acc);
+    dx[i * lddx + d] = acc;
+}
+
+// text_proj weight gradient: dW[e][d] = sum_i dp[i][e] x[i][d] (x rows of stride ldx: the CLS rows of the stream), written
+__global__ __launch_bounds__(256) void head_wgrad_kernel(const float* __restrict__ dp, const float* __restrict__ x, int64_t ldx,
+                                                         float* __restrict__ dW, int B, int E, int D) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    const int64_t e = blockIdx.y;
+    if (d >= D) return;
+    float acc = 0.f;
+    for (int64_t i = 0; i < B; ++i) acc = fmaf(dp[i * E + e], x[i * ldx + d], acc);
+    dW[e * D + d] = acc;
+}
+
+// text_proj bias gradient db[e] = sum_i dp[i][e], and dtemp = -sum_i row_dot[i] / temp (both written, rows in order)
+__global__ __launch_bounds__(256) void head_sums_kernel(const float* __restrict__ dp, const float* __restrict__ row_dot,
+                                                        const float* __restrict__ temp, float* __restrict__ db, float* __restrict__ dtemp,
+                                                        int B, int E) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (db != nullptr && e < E) {
+        float acc = 0.f;
+        for (int64_t i = 0; i < B; ++i) acc += dp[i * E + e];
+        db[e] = acc;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        float acc = 0.f;
+        for (int i = 0; i < B; ++i) acc += row_dot[i];
+        dtemp[0] = -acc / temp[0];
+    }
+}
+
 }  // namespace cir
 
 using namespace cir;
@@ -850,5 +976,44 @@ extern "C" int cir_adamw_step(float* p, const float* g, float* m, float* v, int6
     const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, n, lr, beta1,
                        beta2, eps, weight_decay, bc1, bc2);
+    CIR_LAUNCH_RESULT();
+}
+
+static bool cir_rows_ok(const void* p, int64_t ld) { return cir_aligned16(p) && (ld % 4) == 0; }
+
+extern "C" int cir_contrastive_fwd(const float* p, const float* target, const float* temp, float* p_hat, float* inv_norm, float* logits,
+                                   int B, int Bt, int E, int dtype, void* stream) {
+    CIR_CHECK_PTR(p); CIR_CHECK_PTR(target); CIR_CHECK_PTR(temp); CIR_CHECK_PTR(p_hat); CIR_CHECK_PTR(inv_norm); CIR_CHECK_PTR(logits);
+    if (B <= 0 || Bt <= 0 || E <= 0) return CIR_EINVAL;
+    if (dtype != CIR_F32) return CIR_EDTYPE;
+    if (E > kHeadMaxE || E % 4 != 0 || B > 65535 || (int64_t)B * Bt >= (int64_t(1) << 31)) return CIR_ESHAPE;
+    if (!cir_aligned16(p) || !cir_aligned16(target) || !cir_aligned16(p_hat) || !cir_aligned16(logits) || (reinterpret_cast<uintptr_t>(temp) & 3) ||
+        (reinterpret_cast<uintptr_t>(inv_norm) & 3)) return CIR_EALIGN;
+    hipLaunchKernelGGL(contrastive_fwd_kernel, dim3(B), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, target, temp, p_hat, inv_norm, logits, Bt, E);
+    CIR_LAUNCH_RESULT();
+}
+
+extern "C" int cir_contrastive_bwd(const float* dlogits, const float* target, const float* temp, const float* p_hat, const float* inv_norm,
+                                   float* dp, float* row_scratch, float* dtemp, const float* x, int64_t ldx, const float* W, float* dx, int64_t lddx,
+                                   float* dW, float* db, int D, int B, int Bt, int E, int dtype, void* stream) {
+    CIR_CHECK_PTR(dlogits); CIR_CHECK_PTR(target); CIR_CHECK_PTR(temp); CIR_CHECK_PTR(p_hat); CIR_CHECK_PTR(inv_norm);
+    CIR_CHECK_PTR(dp); CIR_CHECK_PTR(row_scratch); CIR_CHECK_PTR(dtemp);
+    const bool proj = x != nullptr || W != nullptr || dx != nullptr || dW != nullptr || db != nullptr;
+    if (proj && (x == nullptr || W == nullptr || dx == nullptr || dW == nullptr || db == nullptr || D <= 0)) return CIR_EINVAL;
+    if (B <= 0 || Bt <= 0 || E <= 0) return CIR_EINVAL;
+    if (dtype != CIR_F32) return CIR_EDTYPE;
+    if (E > kHeadMaxE || E % 4 != 0 || B > 65535 || (int64_t)B * Bt >= (int64_t(1) << 31)) return CIR_ESHAPE;
+    if (proj && (D % 4 != 0 || ldx < D || lddx < D || (int64_t)(B - 1) * std::max(ldx, lddx) + D >= (int64_t(1) << 40))) return CIR_ESHAPE;
+    if (!cir_aligned16(dlogits) || !cir_aligned16(target) || !cir_aligned16(p_hat) || !cir_aligned16(dp) || (reinterpret_cast<uintptr_t>(temp) & 3) ||
+        (reinterpret_cast<uintptr_t>(inv_norm) & 3) || (reinterpret_cast<uintptr_t>(row_scratch) & 3) || (reinterpret_cast<uintptr_t>(dtemp) & 3))
+        return CIR_EALIGN;
+    if (proj && (!cir_rows_ok(x, ldx) || !cir_rows_ok(dx, lddx) || !cir_aligned16(W) || !cir_aligned16(dW) || !cir_aligned16(db))) return CIR_EALIGN;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(contrastive_bwd_rows_kernel, dim3(B), dim3(256), 0, s, dlogits, target, temp, p_hat, inv_norm, dp, row_scratch, Bt, E);
+    if (proj) {
+        hipLaunchKernelGGL(head_dgrad_kernel, dim3((D + 255) / 256, B), dim3(256), 0, s, dp, W, dx, lddx, E, D);
+        hipLaunchKernelGGL(head_wgrad_kernel, dim3((D + 255) / 256, E), dim3(256), 0, s, dp, x, ldx, dW, B, E, D);
+    }
+    hipLaunchKernelGGL(head_sums_kernel, dim3(proj ? (E + 255) / 256 : 1), dim3(256), 0, s, dp, row_scratch, temp, proj ? db : nullptr, dtemp, B, E);
     CIR_LAUNCH_RESULT();
 }

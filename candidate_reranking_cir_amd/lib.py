@@ -90,6 +90,10 @@ SIGNATURES = {
     "cir_grads_check": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "cir_adamw_begin": (c_int, [c_void_p, c_float, c_float, c_void_p]),
     "cir_adamw_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    # stage-I contrastive head (blip_stage1.py:83-91)
+    "cir_contrastive_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "cir_contrastive_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                    c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

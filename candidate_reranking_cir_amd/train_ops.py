@@ -330,3 +330,43 @@ def adamw_step_dev(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.T
                                               0 if p16 is None else _DT[p16.dtype], _stream()), "cir_adamw_step_dev")
     _lib.PARAM_EPOCH[0] += 1
 
+
+
+def contrastive_fwd(p: torch.Tensor, target: torch.Tensor, temp: torch.Tensor):
+    """Stage-I contrastive head (cir_contrastive_fwd, blip_stage1.py:83-91): p (B, E), target (Bt, E) fp32 contiguous, temp the fp32 scalar
+    parameter (read on the device) -> (p_hat (B, E), inv_norm (B), logits = p_hat target^T / temp (B, Bt))."""
+    _need_cuda(p, target, temp)
+    assert p.dtype == target.dtype == temp.dtype == torch.float32 and p.is_contiguous() and target.is_contiguous() and temp.numel() == 1
+    b, e = p.shape
+    bt = target.shape[0]
+    assert target.shape == (bt, e)
+    p_hat = torch.empty_like(p)
+    inv = torch.empty((b,), dtype=torch.float32, device=p.device)
+    logits = torch.empty((b, bt), dtype=torch.float32, device=p.device)
+    _lib.check(_lib.load().cir_contrastive_fwd(p.data_ptr(), target.data_ptr(), temp.data_ptr(), p_hat.data_ptr(), inv.data_ptr(), logits.data_ptr(),
+                                               b, bt, e, _lib.CIR_F32, _stream()), "cir_contrastive_fwd")
+    return p_hat, inv, logits
+
+
+def contrastive_bwd(dlogits: torch.Tensor, target: torch.Tensor, temp: torch.Tensor, p_hat: torch.Tensor, inv_norm: torch.Tensor, dtemp: torch.Tensor,
+                    x: Optional[torch.Tensor] = None, w: Optional[torch.Tensor] = None, dx: Optional[torch.Tensor] = None,
+                    dw: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adjoint of `contrastive_fwd` (cir_contrastive_bwd): returns dp (B, E); WRITES dtemp (one fp32 element).  With x (B, D) rows (any row
+    stride, unit last stride), w (E, D) = text_proj's weight, dx (B, D) rows, dw (E, D), db (E): text_proj's adjoint as well, all written."""
+    _need_cuda(dlogits, target, temp, p_hat, inv_norm, dtemp, x, w, dx, dw, db)
+    b, e = p_hat.shape
+    bt = target.shape[0]
+    assert dlogits.shape == (b, bt) and dlogits.dtype == torch.float32 and dlogits.is_contiguous() and dtemp.numel() == 1 and dtemp.dtype == torch.float32
+    dp = torch.empty_like(p_hat)
+    scratch = torch.empty((b,), dtype=torch.float32, device=p_hat.device)
+    d, ldx, lddx = 0, 0, 0
+    if x is not None:
+        d = x.shape[1]
+        assert x.shape == (b, d) and dx.shape == (b, d) and x.stride(1) == 1 and dx.stride(1) == 1 and w.shape == (e, d) and w.is_contiguous()
+        assert dw.shape == (e, d) and dw.is_contiguous() and db.shape == (e,) and db.is_contiguous()
+        assert all(t.dtype == torch.float32 for t in (x, w, dx, dw, db))
+        ldx, lddx = x.stride(0), dx.stride(0)
+    _lib.check(_lib.load().cir_contrastive_bwd(dlogits.data_ptr(), target.data_ptr(), temp.data_ptr(), p_hat.data_ptr(), inv_norm.data_ptr(), dp.data_ptr(),
+                                               scratch.data_ptr(), dtemp.data_ptr(), _ptr(x), ldx, _ptr(w), _ptr(dx), lddx, _ptr(dw), _ptr(db), d, b, bt, e,
+                                               _lib.CIR_F32, _stream()), "cir_contrastive_bwd")
+    return dp

@@ -431,6 +431,23 @@ int cir_grads_check(float* g, int64_t n, float scale, int32_t* state, void* stre
 int cir_adamw_begin(int32_t* state, float beta1, float beta2, void* stream);
 int cir_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                        const int32_t* state, void* p16, int dtype16, void* stream);
+/* Contrastive head of the stage-I training step (blip_stage1.py:83-91; driven by stage1_train.py:170-172):
+ *   p_hat = F.normalize(p) = p / max(||p||, 1e-12),   logits = p_hat target^T / temp
+ * p (B, E) fp32 = text_proj of the CLS rows; target (Bt, E) fp32, used as given (the reference's pooled target features are already
+ * normalised); temp = DEVICE pointer to the fp32 scalar parameter (no host read).  Outputs p_hat (B, E), inv_norm (B) = 1 / max(||p||, 1e-12),
+ * logits (B, Bt), all contiguous fp32.
+ * cir_contrastive_bwd, from dlogits (B, Bt):  dp_hat = dlogits target / temp,  dp = (dp_hat - p_hat (p_hat . dp_hat)) inv_norm  (written to dp),
+ * dtemp = -sum dlogits * logits / temp = -sum_i (p_hat_i . dp_hat_i) / temp  WRITTEN (not added) to *dtemp; row_scratch: fp32 (B) work space.
+ * Optionally (x, W, dx, dW, db all given, or all NULL) text_proj's adjoint in the same call: x (B, D) rows at stride ldx (the CLS rows of the
+ * fp32 stream), W (E, D) the text_proj weight; dx (B, D) at stride lddx = dp W, dW (E, D) = dp^T x, db (E) = column sums of dp - all WRITTEN.
+ * Every reduction runs in a fixed order without atomics: the outputs repeat bit for bit.  dtype: CIR_F32 only (CIR_EDTYPE otherwise).
+ * E % 4 == 0, E <= 1024, B <= 65535, B * Bt < 2^31 (CIR_ESHAPE); D % 4 == 0 and ldx, lddx >= D, multiples of 4; 16-byte aligned matrices,
+ * 4-byte aligned scalars / vectors (temp, inv_norm, row_scratch, dtemp). */
+int cir_contrastive_fwd(const float* p, const float* target, const float* temp, float* p_hat, float* inv_norm, float* logits, int B, int Bt, int E,
+                        int dtype, void* stream);
+int cir_contrastive_bwd(const float* dlogits, const float* target, const float* temp, const float* p_hat, const float* inv_norm, float* dp,
+                        float* row_scratch, float* dtemp, const float* x, int64_t ldx, const float* W, float* dx, int64_t lddx, float* dW, float* db,
+                        int D, int B, int Bt, int E, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
