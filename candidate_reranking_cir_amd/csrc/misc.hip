@@ -317,6 +317,7 @@ extern "C" int cir_small_linear(const void* x, int64_t ldx, const void* W, const
     if (N > 8 || K % 8) return CIR_ESHAPE;
     if (dtype != CIR_BF16 && dtype != CIR_F16) return CIR_EDTYPE;
     if (!cir_aligned16(x) || !cir_aligned16(W) || ldx % 8) return CIR_EALIGN;
+    if ((M + 3) / 4 > 0x7fffffffLL) return CIR_ESHAPE;
     dim3 grid((unsigned)((M + 3) / 4)), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == CIR_BF16) hipLaunchKernelGGL((small_linear_kernel<__bf16>), grid, block, 0, s, (const __bf16*)x, ldx, (const __bf16*)W, bias, y, M, N, K);
@@ -472,7 +473,7 @@ extern "C" int cir_linear_f32(const float* x, int64_t ldx, const float* W, const
     if (M <= 0 || N <= 0 || K <= 0) return CIR_EINVAL;
     if (mode < 0 || mode > 2) return CIR_EINVAL;
     dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64)), block(256);
-    if (grid.y > 65535u * 16u) return CIR_ESHAPE;
+    if (grid.y > 65535u) return CIR_ESHAPE;   // one grid dimension holds 65535 blocks: M <= 65535 * 64 rows per call
     hipLaunchKernelGGL(cir::linear_f32_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), x, ldx, W, bias, y, M, N, K, mode);
     CIR_LAUNCH_RESULT();
 }
@@ -480,6 +481,7 @@ extern "C" int cir_linear_f32(const float* x, int64_t ldx, const float* W, const
 extern "C" int cir_l2_normalize(const float* x, float* y, int64_t rows, int cols, void* stream) {
     CIR_CHECK_PTR(x); CIR_CHECK_PTR(y);
     if (rows <= 0 || cols <= 0) return CIR_EINVAL;
+    if ((rows + 3) / 4 > 0x7fffffffLL) return CIR_ESHAPE;
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     hipLaunchKernelGGL(cir::l2_normalize_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), x, y, rows, cols);
     CIR_LAUNCH_RESULT();

@@ -939,6 +939,7 @@ extern "C" int cir_eltwise(const void* z, int z_dtype, const float* dy, void* ou
     CIR_CHECK_PTR(z); CIR_CHECK_PTR(out);
     if (n <= 0 || mode < 0 || mode > 6 || (mode != 6 && (p_drop < 0.f || p_drop >= 1.f))) return CIR_EINVAL;
     if ((mode == 1 || mode == 3 || mode == 5) && dy == nullptr) return CIR_EINVAL;
+    if ((n + 1023) / 1024 > 0x7fffffffLL) return CIR_ESHAPE;
     dim3 grid((unsigned)((n + 1023) / 1024)), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int vec = (reinterpret_cast<uintptr_t>(z) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0 && reinterpret_cast<uintptr_t>(dy) % 16 == 0) ? 1 : 0;
@@ -957,6 +958,7 @@ extern "C" int cir_colsum(const float* x, int64_t ld, float* out, int64_t rows, 
     CIR_CHECK_PTR(x); CIR_CHECK_PTR(out);
     if (rows <= 0 || cols <= 0) return CIR_EINVAL;
     const int64_t rpb = 32;
+    if ((rows + rpb - 1) / rpb > 65535) return CIR_ESHAPE;   // grid.y: 65535 * 32 rows per call
     dim3 grid((cols + 255) / 256, (unsigned)((rows + rpb - 1) / rpb)), block(256);
     hipLaunchKernelGGL(colsum_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), x, ld, out, rows, cols, rpb);
     CIR_LAUNCH_RESULT();
@@ -965,6 +967,7 @@ extern "C" int cir_colsum(const float* x, int64_t ld, float* out, int64_t rows, 
 extern "C" int cir_embed_bwd(const int64_t* ids, const float* dy, float* dword, float* dpos, int64_t rows, int L, int cols, void* stream) {
     CIR_CHECK_PTR(ids); CIR_CHECK_PTR(dy); CIR_CHECK_PTR(dword); CIR_CHECK_PTR(dpos);
     if (rows <= 0 || L <= 0 || cols <= 0) return CIR_EINVAL;
+    if (rows > 0x7fffffffLL) return CIR_ESHAPE;   // one workgroup per row
     hipLaunchKernelGGL(embed_bwd_kernel, dim3((unsigned)rows), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), ids, dy, dword, dpos, rows, L, cols);
     CIR_LAUNCH_RESULT();
 }

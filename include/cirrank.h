@@ -279,8 +279,8 @@ int cir_small_linear(const void* x, int64_t ldx, const void* W, const float* bia
  * dst[i] = convert(src[index[i]]) for rows of `row_elems` elements (index NULL = identity).
  * Replaces the per-query candidate gather torch.stack(itemgetter(*names)(name_to_feat))
  * (validate_stage2.py:115, 251, 266), the `.expand(K, ...)` of z_t / ids to the K candidates
- * (blip_stage2.py:118-121) and dtype conversion at the boundary.  row_elems % 8 == 0; dtype pairs:
- * f32->f32/bf16/f16, bf16->bf16/f32, f16->f16/f32.  Indices are clamped to [0, src_rows).
+ * (blip_stage2.py:118-121) and dtype conversion at the boundary.  row_elems % 8 == 0; every pair of
+ * {f32, bf16, f16} (a conversion rounds once, from the fp32 value).  Indices are clamped to [0, src_rows).
  */
 int cir_gather_rows(const void* src, int src_dtype, const int64_t* index, void* dst, int dst_dtype,
                     int64_t n_rows, int64_t row_elems, int64_t src_rows, void* stream);
@@ -297,6 +297,7 @@ int cir_topk_desc(const float* logits, int64_t* idx, int Q, int K, void* stream)
  * negative of mode 1, so that cir_topk_desc ranks by ascending distance): stage I's 256-d heads
  * vision_proj / text_proj (blip_stage1.py:42-43, 58, 83) and its distance matrix
  * `1 - predicted_features @ index_features.T` (validate.py:57, 202).  x rows at stride ldx.
+ * M <= 65535 * 64 rows per call (CIR_ESHAPE beyond: one grid dimension of 64-row blocks).
  */
 int cir_linear_f32(const float* x, int64_t ldx, const float* W, const float* bias, float* y,
                    int64_t M, int N, int K, int mode, void* stream);
@@ -412,7 +413,7 @@ int cir_rows_scale_add(const float* a, const float* b, const float* scale, void*
 /* mode 0: out = gelu(z) (erf form, ACT2FN['gelu']); 1: out = dy * gelu'(z); 2: relu(z); 3: dy * (z > 0); 4: dropout(z, p_drop, seed);
  * 5: z + dy; 6: p_drop * z (scale).  z in z_dtype (CIR_F32 / CIR_BF16 / CIR_F16), dy fp32, out in out_dtype. */
 int cir_eltwise(const void* z, int z_dtype, const float* dy, void* out, int out_dtype, int64_t n, int mode, float p_drop, uint64_t seed, void* stream);
-/* out[c] += sum_r x[r][c] (bias gradients; fp32, atomics). */
+/* out[c] += sum_r x[r][c] (bias gradients; fp32, atomics).  rows <= 65535 * 32 per call (CIR_ESHAPE beyond). */
 int cir_colsum(const float* x, int64_t ld, float* out, int64_t rows, int cols, void* stream);
 /* BertEmbeddings backward (nlvr_encoder.py:49-91): dword[ids[r]] += dy[r], dpos[r % L] += dy[r] (fp32, atomics). */
 int cir_embed_bwd(const int64_t* ids, const float* dy, float* dword, float* dpos, int64_t rows, int L, int cols, void* stream);
