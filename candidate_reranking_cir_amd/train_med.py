@@ -7,11 +7,12 @@ cross-attention (med.py:225), on the output dense of both attention blocks (med.
 med_config probabilities (0.1).  z_t is therefore a noisy input of the stage-II step, a regulariser the loop relies on.  Rounds 3-5 formed
 z_t with the deterministic inference engine (a stated deviation); this module is the train-mode forward (round 6).
 
-Arithmetic = the training plan of train.py: 16-bit operands, fp32 residual stream, the FUSED training kernels (cir_attention_train_fwd:
-mask + softmax + dropout + P.V in registers; cir_residual_layernorm_train: dropout(dense) + residual + LayerNorm in one pass) on the
-weights of a `MedEngine`.  The draw: one 62-bit base seed per call from torch's global (CPU) generator - `torch.manual_seed` governs it,
-as it governs the reference's - and one counter-based site seed per (layer, site); element numbering as in include/cirrank.h, so the
-masks can be regenerated on the host (tests/helpers.pair_keep / splitmix_keep; tests/test_train_med_gpu.py hands them to the oracle).
+Arithmetic = the training plan of train.py (head views and the seed draw come from train_core.py): 16-bit operands, fp32 residual stream,
+the FUSED training kernels (cir_attention_train_fwd: mask + softmax + dropout + P.V in registers; cir_residual_layernorm_train:
+dropout(dense) + residual + LayerNorm in one pass) on the weights of a `MedEngine`.  The draw: one 62-bit base seed per call from torch's
+global (CPU) generator - `torch.manual_seed` governs it, as it governs the reference's - and one counter-based site seed per (layer, site);
+element numbering as in include/cirrank.h, so the masks can be regenerated on the host (tests/helpers.pair_keep / splitmix_keep;
+tests/test_train_med_gpu.py hands them to the oracle).
 """
 from __future__ import annotations
 
@@ -21,6 +22,7 @@ import torch
 
 from . import ops, train_ops as T
 from .engine import MedEngine, additive_encoder_mask, additive_self_mask
+from .train_core import draw_seed, head_view
 
 # site ids (second argument of `site`): which dropout of a layer
 SITE_EMB, SITE_SELF_ATTN, SITE_SELF_OUT, SITE_CROSS_ATTN, SITE_CROSS_OUT, SITE_FFN_OUT = 0, 1, 2, 3, 4, 5
@@ -43,9 +45,7 @@ class MedDropoutForward:
         self.last_seed: Optional[int] = None
 
     def _heads(self, x: torch.Tensor, groups: int, rows: int, part: int, parts: int) -> torch.Tensor:
-        """(groups * rows, parts * D) projection(s) -> (groups, H, rows, 64) head view of projection `part` (no copy)."""
-        h = self.eng.geo.num_attention_heads
-        return x.view(groups, rows, parts, h, 64)[:, :, part].permute(0, 2, 1, 3)
+        return head_view(x, groups, rows, self.eng.geo.num_attention_heads, 64, part, parts)
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, enc16: torch.Tensor, enc_mask: Optional[torch.Tensor] = None,
@@ -53,9 +53,7 @@ class MedDropoutForward:
         eng = self.eng
         geo, dt = eng.geo, eng.dtype
         ph, pa = self.p_hidden, self.p_attn
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())     # torch's global CPU generator: no device read
-        self.last_seed = seed
+        self.last_seed = seed = draw_seed(seed)
         q_n, l = input_ids.shape
         d, n = geo.hidden_size, enc16.shape[1]
         r = q_n * l

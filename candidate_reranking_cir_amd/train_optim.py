@@ -1,0 +1,194 @@
+"""`AdamW`: torch.optim.AdamW's update rule on cir_adamw_step for the trainers' flat parameter slabs (train_core._Slab), with GradScaler's
+found_inf / skip decision taken on the device; `cosine_lr_schedule`: the reference's per-epoch decay."""
+from __future__ import annotations
+
+import math
+from typing import Dict, NamedTuple, Optional
+
+import torch
+from torch.autograd.graph import increment_version
+
+from . import train_ops as T
+from .train_core import _SLABS, _Slab
+
+
+def cosine_lr_schedule(optimizer, epoch: int, max_epoch: int, init_lr: float, min_lr: float) -> float:
+    """utils.cosine_lr_schedule (utils.py:216-221): the per-epoch decay stage2_train.py:159 applies; works on `AdamW` below and on torch.optim."""
+    lr = (init_lr - min_lr) * 0.5 * (1.0 + math.cos(math.pi * epoch / max_epoch)) + min_lr
+    for group in optimizer.param_groups:
+        group["lr"] = lr
+    return lr
+
+
+class _Work(NamedTuple):
+    """One update launch of `AdamW.step`: flat (or per-tensor) parameters, gradients and moments; the 16-bit copy written along and the
+    slab it belongs to (flat path); the non-contiguous parameter a stepped copy is written back to (per-tensor path)."""
+    p: torch.Tensor
+    g: torch.Tensor
+    m: torch.Tensor
+    v: torch.Tensor
+    p16: Optional[torch.Tensor] = None
+    slab: Optional[_Slab] = None
+    copy_back: Optional[torch.nn.Parameter] = None
+
+
+class AdamW:
+    """torch.optim.AdamW's update rule on cir_adamw_step (stage2_train.py:138 builds that optimizer), fp32 master parameters.
+    When the parameters and their gradients are the trainer's flat buffers (the normal case after `fusion_train`), one launch
+    updates all of them; otherwise one launch per tensor."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, model=None, check_finite=None):
+        """`model`: the BLIP_NLVR whose parameters these are (its trainers' finite flags decide the skip; every step() moves the
+        parameters' version counters, which the packed inference engines and the 16-bit slabs compare, with or without it).
+        `check_finite`: test the gradients step() is about to apply for inf / NaN and skip the update then (GradScaler.step's found_inf,
+        stage2_train.py:215-218; one reduction over the flat gradient buffer + one host read).  None = automatic: always, unless `model`
+        is given and its trainers run bf16 operands (whose pass cannot overflow: no loss scale)."""
+        self.model = model
+        self.check_finite = check_finite
+        self.params = [p for p in params if p.requires_grad]
+        self.betas, self.eps, self.wd = betas, eps, weight_decay
+        self._state = None                                    # device: [found_inf, t, skipped, bc1, bc2, ...] (cir_adamw_begin)
+        self._calls = 0
+        self._plans: Dict[tuple, tuple] = {}                  # (param storage, first param) -> cached flat layout of a parameter group
+        # torch.optim's surface as far as the reference's loop uses it: utils.cosine_lr_schedule (utils.py:216-221, called once per epoch at
+        # stage2_train.py:159) writes `param_group['lr']`; one group, its 'lr' is what step() applies
+        self.param_groups = [{"params": self.params, "lr": lr, "betas": betas, "eps": eps, "weight_decay": weight_decay}]
+        self.m: Dict[int, torch.Tensor] = {}
+        self.v: Dict[int, torch.Tensor] = {}
+        self._flats: Dict[int, tuple] = {}                    # param storage ptr -> (m flat, v flat)
+
+    @property
+    def lr(self) -> float:
+        return self.param_groups[0]["lr"]
+
+    @lr.setter
+    def lr(self, value: float):
+        self.param_groups[0]["lr"] = value
+
+    @staticmethod
+    def _flat_range(tensors):
+        """(base pointer, elements) when `tensors` tile ONE storage completely in slices padded to 8 elements, else None."""
+        st = tensors[0].untyped_storage()
+        if any(t.untyped_storage().data_ptr() != st.data_ptr() or not t.is_contiguous() for t in tensors):
+            return None
+        if sum((t.numel() + 7) // 8 * 8 for t in tensors) * 4 != st.nbytes():
+            return None
+        return st.data_ptr(), st.nbytes() // 4
+
+    # applied / skipped step counts live on the device (the skip decision is taken there): reading them is a host read
+    @property
+    def t(self) -> int:
+        return 0 if self._state is None else int(self._state[1])
+
+    @property
+    def skipped_steps(self) -> int:
+        return 0 if self._state is None else int(self._state[2])
+
+    def _plan(self, grp):
+        """Flat layout of a group of parameters that tile ONE fp32 storage (the trainer's slab): (base pointer, elements, per-parameter
+        element offsets) - computed once per group; None when they do not tile one."""
+        key = (grp[0].data.untyped_storage().data_ptr(), len(grp), id(grp[0]), id(grp[-1]))
+        if key not in self._plans:
+            fp = self._flat_range([p.data for p in grp])
+            self._plans[key] = None if fp is None else (fp[0], fp[1], [(p.data_ptr() - fp[0]) // 4 for p in grp])
+        return self._plans[key]
+
+    @staticmethod
+    def _grads_match(grp, plan):
+        """The gradients of `grp` are slices of ONE flat buffer laid out like the parameters (what the trainers install): its base pointer."""
+        g0 = grp[0].grad
+        base = g0.data_ptr() - 4 * plan[2][0]
+        if g0.untyped_storage().data_ptr() != base or g0.untyped_storage().nbytes() != 4 * plan[1]:
+            return None
+        for p, o in zip(grp, plan[2]):
+            g = p.grad
+            if g.data_ptr() != base + 4 * o or g.dtype != torch.float32 or not g.is_contiguous():
+                return None
+        return base
+
+    @torch.no_grad()
+    def step(self):
+        """One AdamW step; with fp16 operands the update is skipped when a gradient is inf / NaN (GradScaler.step, stage2_train.py:215-218).
+        Nothing here reads the device (round 6): the finite test ORs into a device flag, cir_adamw_begin turns it into the step count /
+        bias corrections or the skip count, and the update kernels return at once under a set flag.  The test runs on the buffers this call
+        APPLIES - .grad as it is now, after any accumulation over micro-batches - and does not depend on `model=`."""
+        ps = [p for p in self.params if p.grad is not None]
+        if not ps:
+            return
+        dev = ps[0].device
+        if self._state is None:
+            self._state = torch.zeros((8,), dtype=torch.int32, device=dev)
+        st = self._state
+        self._calls += 1
+        st[0:1].zero_()
+        need = self.check_finite
+        trainers = [] if self.model is None else [tr for tr in (getattr(self.model, "_trainer", None), getattr(self.model, "_vit_trainer", None)) if tr is not None]
+        if need is None:
+            need = self.model is None or not trainers or any(getattr(tr, "dtype", None) == torch.float16 for tr in trainers)
+        for tr in trainers:                                   # a flag a trainer's last backward (or a test / caller) set
+            gf = getattr(tr, "grads_finite", None)
+            if gf is not None:
+                st[0:1] |= (~torch.as_tensor(gf, device=dev).reshape(1)).to(torch.int32)
+        # one launch per FLAT STORAGE (the two-branch encoder's slab; the ViT's when it is fine-tuned), per tensor for what is left
+        groups: Dict[int, list] = {}
+        for p in ps:
+            groups.setdefault(p.data.untyped_storage().data_ptr(), []).append(p)
+        work = []
+        for grp in groups.values():
+            plan = self._plan(grp) if len(grp) > 1 else None
+            gbase = self._grads_match(grp, plan) if plan is not None else None
+            if gbase is None:
+                for p in grp:
+                    if id(p) not in self.m:
+                        self.m[id(p)], self.v[id(p)] = torch.zeros_like(p, dtype=torch.float32), torch.zeros_like(p, dtype=torch.float32)
+                    m, v = self.m[id(p)], self.v[id(p)]
+                    if not (m.is_contiguous() and v.is_contiguous()):
+                        m, v = self.m[id(p)], self.v[id(p)] = m.contiguous(), v.contiguous()
+                    pd = p.data if p.data.is_contiguous() and p.data_ptr() % 16 == 0 else None       # (else: stepped through a copy)
+                    g = p.grad.contiguous().float()
+                    work.append(_Work(pd if pd is not None else p.data.contiguous().clone(), g if g.data_ptr() % 16 == 0 else g.clone(), m, v,
+                                      copy_back=None if pd is not None else p))
+                continue
+            n = plan[1]
+            flat = self._flats.get(plan[0])
+            if flat is None:
+                mf, vf = (torch.zeros((n,), dtype=torch.float32, device=dev) for _ in range(2))
+                for p, o in zip(grp, plan[2]):                # carry over moments from per-tensor steps, then keep views
+                    for store, fl in ((self.m, mf), (self.v, vf)):
+                        view = fl[o:o + p.numel()].view(p.shape)
+                        if id(p) in store:
+                            view.copy_(store[id(p)])
+                        store[id(p)] = view
+                flat = self._flats[plan[0]] = (mf, vf)
+            pflat = torch.empty(0, dtype=torch.float32, device=dev).set_(grp[0].data.untyped_storage(), 0, (n,))
+            gflat = torch.empty(0, dtype=torch.float32, device=dev).set_(grp[0].grad.untyped_storage(), 0, (n,))
+            slab = _SLABS.get(plan[0])                        # the trainer's slab these parameters live in: its 16-bit copy is written along
+            slab = slab() if slab is not None else None
+            if slab is not None and (slab.flat32.data_ptr() != plan[0] or slab.flat16 is None or slab.flat16.numel() != n):
+                slab = None
+            work.append(_Work(pflat, gflat, flat[0], flat[1], None if slab is None else slab.flat16, slab))
+        if need:
+            for w in work:
+                # the trainer's backward tested exactly this buffer and no torch op has written to it since (version counter of the buffer
+                # and its views): its flag stands; anything else - accumulated sums, edited gradients, foreign buffers - is tested here
+                ck = None if w.slab is None else w.slab.checked
+                if ck is not None and ck[0] == w.g.data_ptr() and w.slab.gflat is not None and w.slab.gflat.data_ptr() == ck[0] and w.slab.gflat._version == ck[2]:
+                    st[0:1] |= (~ck[1].reshape(1)).to(torch.int32)
+                else:
+                    T.grads_check(w.g, st)
+        T.adamw_begin(st, self.betas)
+        for w in work:
+            T.adamw_step_dev(w.p, w.g, w.m, w.v, st, self.lr, self.betas, self.eps, self.wd, p16=w.p16)
+            if w.copy_back is not None:                       # (a non-contiguous parameter stepped through a contiguous copy)
+                w.copy_back.data.copy_(w.p)
+        # the kernels wrote through pointers: move the parameters' version counters, which the packed copies (engines, graphs, K/V banks,
+        # slabs) compare - then the slabs whose 16-bit copy was written along record the key as it now is (all of them: a slab marked before
+        # a later launch of this step would re-cast at its next step)
+        increment_version(ps)
+        for w in work:
+            if w.slab is not None:
+                w.slab.mark_fresh16()                         # (a skipped step leaves both copies as they were: still consistent)
+
+    def zero_grad(self):
+        for p in self.params:
+            p.grad = None

@@ -10,8 +10,8 @@ position embeddings and the embedding LayerNorm, text_proj and temp - 319 tensor
 runs under no_grad, so it receives none.
 
 `MedTrainer` runs that forward with what the backward needs kept on the device and the backward as an explicit reverse pass, as
-train.NlvrTrainer does for stage II (same parameter slab, dense layers, fused attention / dropout + residual + LayerNorm kernels and
-their adjoints, one grouped weight-gradient launch per layer), with a single branch:
+train.NlvrTrainer does for stage II (the shared machinery is in train_core.py: same parameter slab, dense layers, fused attention /
+dropout + residual + LayerNorm kernels and their adjoints, one grouped weight-gradient launch per layer), with a single branch:
   - one attention group per query: the self-attention over its L caption rows with the key mask, the cross-attention of its L rows
     against the N tokens of ITS OWN reference image (no mask: the reference's image masks are all ones);
   - the cross K|V projection of all B * N reference tokens, cast to 16 bits once per step; its weight gradient contracts over B * N rows
@@ -24,33 +24,34 @@ MedDropoutForward draws.
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List
 
 import torch
 
 from . import ops, train_ops as T
 from .engine import additive_self_mask
-from .train import _LN, _Lin, _Slab, _install_grads, _unscale_and_check, train_dtype
+from .train_core import Trainer, _install_grads, draw_seed, loss_scale, train_dtype
 from .train_med import SITE_CROSS_ATTN, SITE_CROSS_OUT, SITE_EMB, SITE_FFN_OUT, SITE_SELF_ATTN, SITE_SELF_OUT, site_seed
 
 INDEX_LIMIT = 2 ** 31          # largest element count of one saved K|V / token tensor the int32-indexed paths accept
 
 
-class MedTrainer:
+class MedTrainer(Trainer):
     """Forward (with saved activations) and backward of the stage-I MED encoder + text_proj + contrastive head for a B x Bt batch."""
 
-    _EMB = "text_encoder.embeddings."
+    _KEY, _NAME = "stage1_train", "img_txt_fusion (stage-I train mode)"
+    # Slab order (train_core.slab_order): the q, k, v weights (then biases) of each self-attention and the k, v weights (then biases) of
+    # each cross-attention adjacent - ONE stacked Linear each; everything else in the model's own order
+    _GROUPS = ([f"attention.self.{x}" for x in ("query", "key", "value")], [f"crossattention.self.{x}" for x in ("key", "value")])
 
     def __init__(self, model):
         self.model = model
         self.geo = geo = model.bert_geometry
         self.p_hidden, self.p_attn = float(geo.hidden_dropout_prob), float(geo.attention_probs_dropout_prob)
         self.dtype = train_dtype(model)
-        self._hd = geo.hidden_size // geo.num_attention_heads
+        self._nh, self._hd = geo.num_attention_heads, geo.hidden_size // geo.num_attention_heads
         self._scale = self._hd ** -0.5
         self.last_seed = None
-        self.grads_finite = None
 
     # ------------------------------------------------------------------------------------------------ parameters
     def _trained(self, name: str) -> bool:
@@ -60,55 +61,8 @@ class MedTrainer:
         return name.startswith(("text_encoder.encoder.layer.", "text_proj.")) or name in (
             "temp", e + "word_embeddings.weight", e + "position_embeddings.weight", e + "LayerNorm.weight", e + "LayerNorm.bias")
 
-    @staticmethod
-    def _order(names: List[str]) -> List[str]:
-        """Slab order: the q, k, v weights (then biases) of each self-attention and the k, v weights (then biases) of each cross-attention
-        adjacent - ONE stacked Linear each (`_Slab.span`); everything else in the model's own order."""
-        groups = {}
-        for n in names:
-            if n.endswith(".attention.self.query.weight"):
-                stem = n[:-len("query.weight")]
-                groups[n] = [stem + q + "." + y for y in ("weight", "bias") for q in ("query", "key", "value")]
-            elif n.endswith(".crossattention.self.key.weight"):
-                stem = n[:-len("key.weight")]
-                groups[n] = [stem + q + "." + y for y in ("weight", "bias") for q in ("key", "value")]
-        grouped = {m for g in groups.values() for m in g}
-        out, seen = [], set()
-        for n in names:
-            if n in seen:
-                continue
-            if n in groups:
-                for m in groups[n]:
-                    out.append(m); seen.add(m)
-            elif n not in grouped:
-                out.append(n); seen.add(n)
-        for n in names:
-            if n not in seen:
-                out.append(n); seen.add(n)
-        assert sorted(out) == sorted(names)
-        return out
-
-    def _pack(self):
-        slab = getattr(self, "slab", None)
-        if slab is None or slab.dtype != self.dtype or not slab.valid():           # first step, or the model was moved / re-cast
-            P = dict(self.model.named_parameters())
-            slab = self.slab = _Slab(P, self._order([n for n in P if self._trained(n)]), self.dtype,
-                                     key=lambda: self.model.weights_key("stage1_train"))
-            slab.begin_step()
-            self._build_layers(slab)
-        slab.begin_step()
-        e = self._EMB
-        self.dword, self.dpos = slab.grad(e + "word_embeddings.weight"), slab.grad(e + "position_embeddings.weight")
-
-    def _build_layers(self, slab: _Slab):
-        g = self.geo
-        lins: List[_Lin] = []
-
-        def lin(name, group=False):
-            lins.append(_Lin(slab, name, group))
-            return lins[-1]
-        ln = lambda name: _LN(slab, name, g.layer_norm_eps)
-        e = self._EMB
+    def _build_layers(self, slab, lin, ln):
+        g, e = self.geo, self._EMB
         self.word, self.pos = slab.w32(e + "word_embeddings.weight"), slab.w32(e + "position_embeddings.weight")
         self.ln_e = ln(e + "LayerNorm")
         self.layers: List[Dict] = []
@@ -124,11 +78,6 @@ class MedTrainer:
         self.tp_w, self.tp_b = slab.w32("text_proj.weight"), slab.w32("text_proj.bias")
         ot = slab.off["temp"]
         self.temp, self._temp_off = slab.flat32[ot:ot + 1], ot                      # (the scalar parameter's slice: read on the device)
-        slab.plan = T.TransposePlan([l.transpose_entry for l in lins], slab.flat32.device)
-
-    def _heads(self, x: torch.Tensor, groups: int, rows: int, part: int = 0, parts: int = 1) -> torch.Tensor:
-        """(groups * rows, parts * D) projection(s) -> (groups, H, rows, head_dim) view of projection `part` (no copy)."""
-        return x.view(groups, rows, parts, self.geo.num_attention_heads, self._hd)[:, :, part].permute(0, 2, 1, 3)
 
     # ------------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
@@ -145,9 +94,7 @@ class MedTrainer:
             raise ValueError(f"stage-I training batch too large: B * N * max(2 * hidden, width) = {q_n * n * max(2 * d, dv)} elements in one "
                              f"tensor (limit {INDEX_LIMIT - 1}: the kernels index with 32-bit offsets) - split the batch (micro-batches accumulate)")
         self._pack()
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())     # torch's global CPU generator: no device read
-        self.last_seed = seed
+        self.last_seed = seed = draw_seed(seed)
         dev = self.word.device
         ph, pa, f32 = self.p_hidden, self.p_attn, torch.float32
         r = q_n * l
@@ -208,10 +155,7 @@ class MedTrainer:
         r = q_n * l
         ph, pa = self.p_hidden, self.p_attn
         # the power-of-two loss scale of NlvrTrainer.backward (fp16 operands: intermediate gradients in fp16's normal range; bf16: none)
-        self.grad_scale = 1.0
-        if dt == torch.float16:
-            amax = float(dlogits.abs().max())
-            self.grad_scale = 2.0 ** round(math.log2(512.0 / amax)) if amax > 0 and math.isfinite(amax) else 1.0
+        self.grad_scale = loss_scale(float(dlogits.abs().max())) if dt == torch.float16 else 1.0
         dl = dlogits.contiguous().float()
         if self.grad_scale != 1.0:
             dl = T.eltwise(dl, T.MODE_SCALE, p_drop=self.grad_scale)
@@ -250,9 +194,7 @@ class MedTrainer:
         de = dh if ph <= 0 else T.eltwise(dh, T.MODE_DROPOUT, p_drop=ph, seed=site_seed(seed, 0, SITE_EMB))
         T.embed_bwd(sv["ids"].view(-1), self.ln_e.bwd(sv["pre_e"], de), self.dword, self.dpos, l)
         self.sv = None                                                              # (the saved activations are released with the pass)
-        self.grads_finite = _unscale_and_check(slab.gflat, self.grad_scale) if dt == torch.float16 else None
-        slab.checked = None if self.grads_finite is None else (slab.gflat.data_ptr(), self.grads_finite, slab.gflat._version)
-        return {nm: slab.grad(nm) for nm in slab.names}
+        return self._finish_backward()
 
 
 class _Stage1TrainFn(torch.autograd.Function):
@@ -263,21 +205,13 @@ class _Stage1TrainFn(torch.autograd.Function):
     def forward(ctx, anchor, trainer, ref_tokens, target, ids, mask):
         ctx.trainer = trainer
         out = trainer.forward(ref_tokens, target, ids, mask)
-        trainer.generation = ctx.generation = getattr(trainer, "generation", 0) + 1
-        trainer.consumed = False
+        trainer._claim(ctx)
         return out
 
     @staticmethod
     def backward(ctx, dlogits):
         tr = ctx.trainer
-        if tr.generation != ctx.generation:
-            raise RuntimeError("img_txt_fusion (stage-I train mode): another training-mode forward ran before this one's backward - the saved "
-                               "activations belong to the later forward.  Call backward() after each forward (gradients accumulate in .grad), "
-                               "or run the other forward under torch.no_grad() / in .eval() mode")
-        if tr.consumed:
-            raise RuntimeError("img_txt_fusion (stage-I train mode): second backward through the same forward (retain_graph): the hand-written "
-                               "reverse pass keeps one set of saved activations per forward; run the forward again")
-        tr.consumed = True
+        tr._consume(ctx)
         _install_grads(tr, tr.backward(dlogits.contiguous().float()))
         return None, None, None, None, None, None
 

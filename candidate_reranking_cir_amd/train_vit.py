@@ -10,33 +10,36 @@ deterministic and is what tests/golden/train_imgtune.npz pins.
 Same construction as `train.NlvrTrainer`: an explicit forward that keeps what the reverse pass needs and a hand-written reverse pass on the
 libcirrank kernels - 16-bit MFMA operands, fp32 residual stream and gradients of it, the fused attention pair (197 / 577 keys, no mask, no
 dropout: the dropout-free instantiations), the four weight gradients of a block in one grouped launch, parameters / 16-bit copies / gradients
-in flat buffers (`train._Slab`) so that `train.AdamW` updates the ViT in one launch.  Pre-LayerNorm blocks: x + f(LayerNorm(x)), so the
-LayerNorm adjoint's input is the saved residual stream itself and its result is added to the skip gradient.
+in flat buffers (`train_core._Slab`; the machinery the passes share is in train_core.py) so that `train.AdamW` updates the ViT in one
+launch.  Pre-LayerNorm blocks: x + f(LayerNorm(x)), so the LayerNorm adjoint's input is the saved residual stream itself and its result is
+added to the skip gradient.
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List
 
 import torch
 
 from . import lib as _lib
 from . import ops, train_ops as T
-from .train import _Lin, _LN, _Slab, _cast, _install_grads, _unscale_and_check
+from .train_core import _LN, Trainer, _cast, _install_grads, loss_scale
 
 _P = "visual_encoder."
 
 
 def vit_train_dtype(model) -> torch.dtype:
     """Operand type of the ViT's training step: the model's token type when it is 16-bit, fp16 under the exact mode (fp32 tokens) - the
-    same mapping `train.train_dtype` applies to the text side (the reference trains under fp16 autocast, stage2_train.py:210-218)."""
+    same mapping `train_core.train_dtype` applies to the text side (the reference trains under fp16 autocast, stage2_train.py:210-218)."""
     return model.token_dtype if model.token_dtype in (torch.float16, torch.bfloat16) else torch.float16
 
 
-class VitTrainer:
+class VitTrainer(Trainer):
+    _KEY = "vit"
+
     def __init__(self, model):
         self.model, self.geo = model, model.vit_geometry
         self.dtype = vit_train_dtype(model)
+        self._nh, self._hd = self.geo.num_heads, 64
         self._scale = 64 ** -0.5                                                    # vit.py:50 (head dimension 64)
         self.seed, self.step_no = 0, 0
 
@@ -54,34 +57,21 @@ class VitTrainer:
     def _trained(self, name: str) -> bool:
         return name.startswith(_P)
 
-    def _pack(self):
-        slab = getattr(self, "slab", None)
-        if slab is None or slab.dtype != self.dtype or not slab.valid():
-            P = {n: p for n, p in self.model.named_parameters() if self._trained(n)}
-            slab = self.slab = _Slab(P, list(P), self.dtype, key=lambda: self.model.weights_key("vit"))
-            slab.begin_step()
-            lins: List[_Lin] = []
-
-            def lin(name):
-                lins.append(_Lin(slab, name))
-                return lins[-1]
-            ln = lambda name: _LN(slab, name, self.geo.layer_norm_eps)
-            self.pe = lin(_P + "patch_embed.proj")                                  # Conv2d(3, D, p, p, stride p) == Linear over flattened patches
-            self.blocks: List[Dict] = []
-            for i in range(self.geo.depth):
-                b = f"{_P}blocks.{i}."
-                self.blocks.append(dict(ln1=ln(b + "norm1"), qkv=lin(b + "attn.qkv"), proj=lin(b + "attn.proj"), ln2=ln(b + "norm2"),
-                                        fc1=lin(b + "mlp.fc1"), fc2=lin(b + "mlp.fc2")))
-            self.lnf = ln(_P + "norm")
-            slab.plan = T.TransposePlan([l.transpose_entry for l in lins], slab.flat32.device)
-        slab.begin_step()
+    def _build_layers(self, slab, lin, ln):
+        self.pe = lin(_P + "patch_embed.proj")                                      # Conv2d(3, D, p, p, stride p) == Linear over flattened patches
+        self.blocks: List[Dict] = []
+        for i in range(self.geo.depth):
+            b = f"{_P}blocks.{i}."
+            self.blocks.append(dict(ln1=ln(b + "norm1"), qkv=lin(b + "attn.qkv"), proj=lin(b + "attn.proj"), ln2=ln(b + "norm2"),
+                                    fc1=lin(b + "mlp.fc1"), fc2=lin(b + "mlp.fc2")))
+        self.lnf = ln(_P + "norm")
         d = self.geo.width
         self.cls, self.pos = slab.w32(_P + "cls_token").view(d), slab.w32(_P + "pos_embed").view(-1, d)
         assert self.pos.shape[0] == self.geo.num_tokens, "pos_embed does not match the ViT geometry"
-        self.dcls, self.dpos = slab.grad(_P + "cls_token").view(d), slab.grad(_P + "pos_embed").view(-1, d)
 
-    def _heads(self, x: torch.Tensor, bsz: int, n: int, part: int) -> torch.Tensor:
-        return x.view(bsz, n, 3, self.geo.num_heads, 64)[:, :, part].permute(0, 2, 1, 3)
+    def _bind_grads(self, slab):
+        d = self.geo.width
+        self.dcls, self.dpos = slab.grad(_P + "cls_token").view(d), slab.grad(_P + "pos_embed").view(-1, d)
 
     def _ln16(self, ln: _LN, x: torch.Tensor):
         """Pre-LayerNorm: only the 16-bit operand copy is needed (the fp32 input itself is the saved tensor of the adjoint)."""
@@ -107,7 +97,7 @@ class VitTrainer:
         # reference and the target images in `blip_bs` mini-batches, every call with a graph (stage2_train.py:191-199) - several calls
         # are live at once, and each backward must find its own activations and its own DropPath draw (round-4 advisor finding).
         sv = {"patches": patches, "bsz": bsz, "blocks": [], "dp": dp, "dp_rates": dp_rates, "epoch": _lib.PARAM_EPOCH[0]}
-        heads = lambda t, j: self._heads(t, bsz, n, j)
+        heads = lambda t, j: self._heads(t, bsz, n, j, 3)
 
         def branch(lin, a16, res, i, j):
             """res + DropPath(lin(a16)) (vit.py:108-109): the residual joins in the GEMM epilogue unless block i drops samples."""
@@ -119,7 +109,7 @@ class VitTrainer:
             qkv = blk["qkv"].fwd(h16, dt)                                            # (B N, 3 D), vit.py:72
             ctx = torch.empty((bsz * n, d), dtype=dt, device=x.device)
             ctx32 = torch.empty((bsz * n, d), dtype=f32, device=x.device)
-            c4, c32 = ctx.view(bsz, n, geo.num_heads, 64).permute(0, 2, 1, 3), ctx32.view(bsz, n, geo.num_heads, 64).permute(0, 2, 1, 3)
+            c4, c32 = self._heads(ctx, bsz, n), self._heads(ctx32, bsz, n)
             lse = T.attention_train_fwd(heads(qkv, 0), heads(qkv, 1), heads(qkv, 2), None, c4, self._scale, 0.0, 0, out32=c32)    # vit.py:73-83
             x1 = branch(blk["proj"], ctx, x, i, 0)                                  # vit.py:84, :108
             _, h2 = self._ln16(blk["ln2"], x1)
@@ -138,7 +128,7 @@ class VitTrainer:
     def backward(self, dfeats: torch.Tensor, sv: Dict = None) -> Dict[str, torch.Tensor]:
         """dfeats (B, N, D) fp32 -> {parameter name: fp32 gradient} for every visual_encoder.* parameter, from the saved state `sv` of
         the forward call being differentiated (default: the latest call's).  Every backward writes a FRESH flat gradient buffer
-        (`train._install_grads` folds it into .grad with one flat add), so the mini-batches of one step - and their loss scales - do
+        (`train_core._install_grads` folds it into .grad with one flat add), so the mini-batches of one step - and their loss scales - do
         not meet inside a buffer."""
         sv = self.sv if sv is None else sv
         geo, dt = self.geo, self.dtype
@@ -147,8 +137,8 @@ class VitTrainer:
                                "the reverse pass would run on other weights than the forward did")
         slab = self.slab
         slab.gflat = torch.zeros_like(slab.flat32)
+        self._bind_grads(slab)
         d = geo.width
-        self.dcls, self.dpos = slab.grad(_P + "cls_token").view(d), slab.grad(_P + "pos_embed").view(-1, d)
         bsz, n = sv["bsz"], geo.num_tokens
         dev = dfeats.device
         g = dfeats.contiguous().float().view(bsz * n, d)
@@ -163,12 +153,11 @@ class VitTrainer:
                 self.grad_scale = float(hint)
                 self.model._trainer.dfeats_scale = None
             else:
-                amax = float(g.abs().max())
-                self.grad_scale = 2.0 ** round(math.log2(512.0 / amax)) if amax > 0 and math.isfinite(amax) else 1.0
+                self.grad_scale = loss_scale(float(g.abs().max()))
             if self.grad_scale != 1.0:
                 g = T.eltwise(g, T.MODE_SCALE, p_drop=self.grad_scale)
         g = self.lnf.bwd(sv["xf"], g)
-        heads = lambda t, j: self._heads(t, bsz, n, j)
+        heads = lambda t, j: self._heads(t, bsz, n, j, 3)
         dp, dp_rates = sv["dp"], sv["dp_rates"]
 
         def branch_grad(gq, i, j):
@@ -187,7 +176,7 @@ class VitTrainer:
             g16 = branch_grad(g, i, 0)
             dctx16 = blk["proj"].bwd16(s["ctx"], g16, dx_dtype=dt, bias=True, queue=wq)
             dqkv16 = torch.empty((bsz * n, 3 * d), dtype=dt, device=dev)
-            c4 = lambda t: t.view(bsz, n, geo.num_heads, 64).permute(0, 2, 1, 3)
+            c4 = lambda t: self._heads(t, bsz, n)
             T.attention_train_bwd(heads(s["qkv"], 0), heads(s["qkv"], 1), heads(s["qkv"], 2), None, c4(s["ctx"]), c4(dctx16), s["lse"],
                                   heads(dqkv16, 0), heads(dqkv16, 1), heads(dqkv16, 2), self._scale, 0.0, 0, out32=c4(s["ctx32"]))
             dh = blk["qkv"].bwd16(s["h16"], dqkv16, bias=True, queue=wq)
@@ -199,11 +188,7 @@ class VitTrainer:
         T.colsum(g3[:, 0], self.dcls)
         dproj16 = _cast(g3[:, 1:].contiguous().view(bsz * (n - 1), d), dt)
         self.pe.bwd16(sv["patches"], dproj16, need_dx=False, bias=True)             # pixels are inputs
-        self.grads_finite = _unscale_and_check(slab.gflat, self.grad_scale) if dt == torch.float16 else None      # (one pass: train.py)
-        slab.checked = None if self.grads_finite is None else (slab.gflat.data_ptr(), self.grads_finite, slab.gflat._version)
-        if dt != torch.float16 and self.grad_scale != 1.0:
-            slab.gflat = T.eltwise(slab.gflat, T.MODE_SCALE, p_drop=1.0 / self.grad_scale)
-        return {name: slab.grad(name) for name in slab.names}
+        return self._finish_backward()
 
 
 class _VitTrainFn(torch.autograd.Function):

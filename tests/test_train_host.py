@@ -36,6 +36,30 @@ def test_trained_set_and_slab_order():
     assert all(torch.Size(spec[n][0]).numel() % 8 == 0 for n in order if ".self" in n)
 
 
+def test_stage1_trained_set_and_slab_order():
+    """MedTrainer: the 319 tensors the stage-I step trains (tests/golden/train_s1.npz), each self-attention's q | k | v and each
+    cross-attention's k | v as one stacked Linear - weights adjacent, then the biases."""
+    from candidate_reranking_cir_amd.train_stage1 import MedTrainer
+    g, v = config.BertGeometry(), config.VitGeometry(image_size=64, depth=1)
+    spec = weights.retrieval_param_spec(g, v)
+    tr = MedTrainer.__new__(MedTrainer)
+    names = [n for n in spec if tr._trained(n)]
+    assert len(names) == 319
+    assert "temp" in names and not any("token_type" in n or n.startswith(("visual_encoder.", "vision_proj.")) for n in names)
+    order = MedTrainer._order(names)
+    assert sorted(order) == sorted(names) and len(set(order)) == len(order)
+    pos = {n: i for i, n in enumerate(order)}
+    for layer in (0, 11):
+        p = f"text_encoder.encoder.layer.{layer}."
+        i = pos[p + "attention.self.query.weight"]
+        assert [order[i + j] for j in range(6)] == [p + f"attention.self.{x}.{y}" for y in ("weight", "bias") for x in ("query", "key", "value")]
+        i = pos[p + "crossattention.self.key.weight"]
+        assert [order[i + j] for j in range(4)] == [p + f"crossattention.self.{x}.{y}" for y in ("weight", "bias") for x in ("key", "value")]
+        # the cross-attention's query is no part of a group: it keeps the model's place, in front of the stacked k | v
+        assert pos[p + "crossattention.self.query.weight"] < pos[p + "crossattention.self.key.weight"]
+    assert all(torch.Size(spec[n][0]).numel() % 8 == 0 for n in order if ".self." in n)
+
+
 def test_row_split():
     assert _row_split(8192, 768, 768) == 16 and _row_split(9232, 768, 768) == 16          # 36 tiles x 16 chunks
     assert _row_split(8192, 3072, 768) == 8 and _row_split(8192, 2304, 768) == 8           # FFN / stacked q|k|v
