@@ -15,6 +15,7 @@
 //     features of one output row -> 16/32/64-byte vector stores, fp32 bias/residual as float4.
 //   * Workgroup -> tile mapping is XCD-aware (blocks that share an XCD's L2 walk neighbouring
 //     tiles of one row panel, so the A panel is fetched from HBM once per XCD).
+//   * All of the above is `Shell128`, shared by gemm_kernel and gemm_split8_kernel: a kernel adds its K-loop body and its own store arms.
 
 #include <type_traits>
 
@@ -49,52 +50,52 @@ __device__ __forceinline__ void mma_frag(f32x4& acc, const typename Elem<T>::x8&
 }
 
 
-// OUT: 0 = C in the operand type T, 1 = fp32 C, 2 = fp16 C (the 16-bit residual stream).  The residual is fp32 for
-// OUT 0 / 1 and fp16 for OUT 2 (element type of the stream it is part of); the sum is formed in fp32 and rounded once.
-template <typename T, int OUT>
-__global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {
-    constexpr bool OUT_F32 = OUT == 1;
-    using X8 = typename Elem<T>::x8;
-    __shared__ __attribute__((aligned(16))) char smem[4 * kTileBytes];  // [buf][A|W]
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave & 1, wn = wave >> 1;
-    const int r15 = lane & 15, g = lane >> 4;
-
-    // ---- which tile ---------------------------------------------------------------------------
-    const int nblk = gridDim.x;
-    int id = xcd_remap(blockIdx.x, nblk);
-    const int per_batch = a.tiles_m * a.tiles_n;
-    const int z = id / per_batch;
-    id -= z * per_batch;
-    const int tile_m = id / a.tiles_n, tile_n = id - tile_m * a.tiles_n;
-    const int64_t m0 = (int64_t)tile_m * BM;
-    const int n0 = tile_n * BN;
-
-    const T* A = reinterpret_cast<const T*>(a.A) + z * a.sA;
-    const T* W = reinterpret_cast<const T*>(a.W) + z * a.sW;
-
-    // ---- per-lane staging sources: 4 wave-instructions of 8 rows for each operand ---------------
-    const int srow = lane >> 3;                 // row inside the 8-row piece
-    const int schunk = (lane & 7) ^ srow;       // global 16-B chunk this lane fetches (swizzle on the source)
-    const T* a_src[4];
+// ---- the shell of the 128 x 128 kernels: everything gemm_kernel and gemm_split8_kernel share but the MFMA segment of their K loops and
+// their 16-bit / split8 store arms.  T = the element type the operand pointers step in (split8 byte rows are addressed in 2-byte units).
+template <typename T>
+struct Shell128 {
+    int lane, wave, wm, wn, r15, g, z, n0;
+    int64_t m0;
+    const T* a_src[4];   // per-lane staging sources: 4 wave-instructions of 8 rows for each operand
     const T* w_src[4];
+
+    __device__ __forceinline__ explicit Shell128(const GemmArgs& a) {
+        const int tid = threadIdx.x;
+        lane = tid & 63;
+        wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+        wm = wave & 1, wn = wave >> 1;
+        r15 = lane & 15, g = lane >> 4;
+
+        // ---- which tile (XCD-aware: see the header) ----------------------------------------------
+        const int nblk = gridDim.x;
+        int id = xcd_remap(blockIdx.x, nblk);
+        const int per_batch = a.tiles_m * a.tiles_n;
+        z = id / per_batch;
+        id -= z * per_batch;
+        const int tile_m = id / a.tiles_n, tile_n = id - tile_m * a.tiles_n;
+        m0 = (int64_t)tile_m * BM;
+        n0 = tile_n * BN;
+
+        const T* A = reinterpret_cast<const T*>(a.A) + z * a.sA;
+        const T* W = reinterpret_cast<const T*>(a.W) + z * a.sW;
+        const int srow = lane >> 3;                 // row inside the 8-row piece
+        const int schunk = (lane & 7) ^ srow;       // global 16-B chunk this lane fetches (swizzle on the source)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int lrow = (wave * 4 + j) * 8 + srow;           // LDS row 0..127
-        int64_t gm = m0 + lrow;
-        gm = gm < a.M ? gm : a.M - 1;                         // clamp the ragged M edge (stores are predicated)
-        a_src[j] = A + gm * a.lda + schunk * Tile<T>::kChunk;
-        // W rows are permuted so that lane group g of the accumulator owns 16 consecutive features
-        const int perm = (lrow & 64) + ((lrow & 15) >> 2) * 16 + ((lrow >> 4) & 3) * 4 + (lrow & 3);
-        int gn = n0 + perm;
-        gn = gn < a.N ? gn : a.N - 1;
-        w_src[j] = W + (int64_t)gn * a.ldw + schunk * Tile<T>::kChunk;
+        for (int j = 0; j < 4; ++j) {
+            const int lrow = (wave * 4 + j) * 8 + srow;           // LDS row 0..127
+            int64_t gm = m0 + lrow;
+            gm = gm < a.M ? gm : a.M - 1;                         // clamp the ragged M edge (stores are predicated)
+            a_src[j] = A + gm * a.lda + schunk * Tile<T>::kChunk;
+            // W rows are permuted so that lane group g of the accumulator owns 16 consecutive features
+            const int perm = (lrow & 64) + ((lrow & 15) >> 2) * 16 + ((lrow >> 4) & 3) * 4 + (lrow & 3);
+            int gn = n0 + perm;
+            gn = gn < a.N ? gn : a.N - 1;
+            w_src[j] = W + (int64_t)gn * a.ldw + schunk * Tile<T>::kChunk;
+        }
     }
 
-    auto stage = [&](int kt, int buf) {
+    // K-tile kt (128 bytes of every row, whatever they hold) -> LDS buffer buf, by LDS-DMA
+    __device__ __forceinline__ void stage(char* smem, int kt, int buf) const {
         char* base = smem + buf * 2 * kTileBytes + wave * 4096;
         const int koff = kt * Tile<T>::kBK;
 #pragma unroll
@@ -105,17 +106,26 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {
         for (int j = 0; j < 4; ++j) {
             __builtin_amdgcn_global_load_lds((gptr_t)(w_src[j] + koff), (lptr_t)(base + kTileBytes + j * 1024), 16, 0, 0);
         }
-    };
+    }
+
+    // Head of K-loop iteration kt: tile kt has landed, tile kt + 1 is on its way; returns tile kt's A image (W follows at + kTileBytes).
+    __device__ __forceinline__ const char* next_tile(char* smem, int kt, int nk) const {
+        // The LDS-DMA pieces of tile kt must have landed before any wave reads them.  The wait is EXPLICIT: hipcc's wait-count
+        // pass dropped the vmcnt(0) it used to put in front of this barrier once a VGPR-destination load (the bias) preceded
+        // the loop (round 4: every K >= 128 result wrong, K = 64 right) - do not rely on it for DMA-written LDS.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();  // tile kt landed everywhere; buffer (kt+1)&1 is free again
+        if (kt + 1 < nk) stage(smem, kt + 1, (kt + 1) & 1);
+        return smem + (kt & 1) * 2 * kTileBytes;
+    }
 
     // Accumulators start at the bias, as in the 256 x 256 kernel: the two kernels then form every output with the SAME sequence
     // of fp32 operations (bias, then the K-steps in ascending order through the same MFMA shape), so which tile size the
     // dispatcher picks - it depends on the batch size - never changes a bit of the result.
-    f32x4 acc[4][4];
-    {
-        const int nb_ = n0 + wn * 64 + g * 16;
+    __device__ __forceinline__ void init_acc(const GemmArgs& a, f32x4 (&acc)[4][4]) const {
         float bias_[16];
-        if (a.bias != nullptr && nb_ + 16 <= a.N) {
-            const float4* bp = reinterpret_cast<const float4*>(a.bias + z * a.sBias + nb_);
+        if (a.bias != nullptr && nb() + 16 <= a.N) {
+            const float4* bp = reinterpret_cast<const float4*>(a.bias + z * a.sBias + nb());
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float4 b4 = bp[q];
@@ -132,29 +142,76 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {
     }
 
     // fragment read offsets (bytes) inside a tile: row*128 + ((kc ^ (row&7)) << 4)
-    const int a_row_off = (wm * 64 + r15) * 128;
-    const int w_row_off = (wn * 64 + r15) * 128;
-    const int swz = r15 & 7;
+    __device__ __forceinline__ int a_row_off() const { return (wm * 64 + r15) * 128; }
+    __device__ __forceinline__ int w_row_off() const { return (wn * 64 + r15) * 128; }
+    __device__ __forceinline__ int chunk_off(int kc) const { return ((kc + g) ^ (r15 & 7)) << 4; }
+
+    // epilogue: lane (r15, g) owns, per mi, row m = row(mi) and features nb() .. nb() + 15 (acc[mi] as 16 floats)
+    __device__ __forceinline__ int nb() const { return n0 + wn * 64 + g * 16; }
+    __device__ __forceinline__ int64_t row(int mi) const { return m0 + wm * 64 + mi * 16 + r15; }
+    static __device__ __forceinline__ void unpack(const f32x4 (&acc)[4], float (&v)[16]) {
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj) v[ni * 4 + jj] = acc[ni][jj];
+    }
+    __device__ __forceinline__ void add_res_f32(const GemmArgs& a, int64_t m, float (&v)[16]) const {
+        const float4* rp = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.R) + z * a.sR + m * a.ldr + nb());
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 r4 = rp[q];
+            v[q * 4 + 0] += r4.x; v[q * 4 + 1] += r4.y; v[q * 4 + 2] += r4.z; v[q * 4 + 3] += r4.w;
+        }
+    }
+    __device__ __forceinline__ void store_f32(const GemmArgs& a, int64_t m, const float (&v)[16]) const {
+        float4* cp = reinterpret_cast<float4*>(reinterpret_cast<float*>(a.C) + z * a.sC + m * a.ldc + nb());
+#pragma unroll
+        for (int q = 0; q < 4; ++q) cp[q] = make_float4(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]);
+    }
+};
+
+// GELU by the 256 x 256 kernel's packed evaluation (the same operations, the same bits; ERF_AS: gelu_erf_as8, the split8 kernels' form), or ReLU
+template <bool ERF_AS>
+__device__ __forceinline__ void act16(int act, float (&v)[16]) {
+    if (act == CIR_ACT_GELU) {
+#pragma unroll
+        for (int q = 0; q < 16; q += 8) {
+            float w8[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) w8[e] = v[q + e];
+            if constexpr (ERF_AS) gelu_erf_as8(w8); else gelu_erf8(w8);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[q + e] = w8[e];
+        }
+    } else if (act == CIR_ACT_RELU) {
+#pragma unroll
+        for (int q = 0; q < 16; ++q) v[q] = fmaxf(v[q], 0.f);
+    }
+}
+
+// OUT: 0 = C in the operand type T, 1 = fp32 C, 2 = fp16 C (the 16-bit residual stream).  The residual is fp32 for
+// OUT 0 / 1 and fp16 for OUT 2 (element type of the stream it is part of); the sum is formed in fp32 and rounded once.
+template <typename T, int OUT>
+__global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {
+    using X8 = typename Elem<T>::x8;
+    __shared__ __attribute__((aligned(16))) char smem[4 * kTileBytes];  // [buf][A|W]
+    const Shell128<T> sh(a);
+    f32x4 acc[4][4];
+    sh.init_acc(a, acc);
 
     const int nk = a.K / Tile<T>::kBK;
-    stage(0, 0);
+    sh.stage(smem, 0, 0);
     for (int kt = 0; kt < nk; ++kt) {
-        // The LDS-DMA pieces of tile kt must have landed before any wave reads them.  The wait is EXPLICIT: hipcc's wait-count
-        // pass dropped the vmcnt(0) it used to put in front of this barrier once a VGPR-destination load (the bias) preceded
-        // the loop (round 4: every K >= 128 result wrong, K = 64 right) - do not rely on it for DMA-written LDS.
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();  // tile kt landed everywhere; buffer (kt+1)&1 is free again
-        if (kt + 1 < nk) stage(kt + 1, (kt + 1) & 1);
-        const char* As = smem + (kt & 1) * 2 * kTileBytes;
+        const char* As = sh.next_tile(smem, kt, nk);
         const char* Ws = As + kTileBytes;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            const int coff = ((ks * 4 + g) ^ swz) << 4;
+            const int coff = sh.chunk_off(ks * 4);
             X8 af[4], wf[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                af[i] = *reinterpret_cast<const X8*>(As + a_row_off + i * 2048 + coff);
-                wf[i] = *reinterpret_cast<const X8*>(Ws + w_row_off + i * 2048 + coff);
+                af[i] = *reinterpret_cast<const X8*>(As + sh.a_row_off() + i * 2048 + coff);
+                wf[i] = *reinterpret_cast<const X8*>(Ws + sh.w_row_off() + i * 2048 + coff);
             }
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
@@ -163,40 +220,25 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {
         }
     }
 
-    // ---- epilogue: lane (r15, g) owns, per mi, row m and features nb .. nb+15 ----------------------
-    const int nb = n0 + wn * 64 + g * 16;
+    const int nb = sh.nb();
     if (nb + 16 > a.N) return;
     const bool has_res = a.R != nullptr;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
-        const int64_t m = m0 + wm * 64 + mi * 16 + r15;
+        const int64_t m = sh.row(mi);
         if (m >= a.M) continue;
         float v[16];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) v[ni * 4 + jj] = acc[mi][ni][jj];
+        sh.unpack(acc[mi], v);
         if (a.act == CIR_ACT_GELU && std::is_same<T, float>::value) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) v[q] = 0.5f * v[q] * (1.0f + erff(v[q] * 0.70710678118654752f));   // ACT2FN['gelu'] / nn.GELU, as written
-        } else if (a.act == CIR_ACT_GELU) {
-#pragma unroll
-            for (int q = 0; q < 16; q += 8) {      // the 256 x 256 kernel's packed evaluation: the same operations, the same bits
-                float w8[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) w8[e] = v[q + e];
-                gelu_erf8(w8);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[q + e] = w8[e];
-            }
-        } else if (a.act == CIR_ACT_RELU) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = fmaxf(v[q], 0.f);
+        } else {
+            act16<false>(a.act, v);
         }
         if (has_res) {
             if constexpr (OUT == 2) {
                 typedef __attribute__((ext_vector_type(8))) _Float16 h8;
-                const h8* rp = reinterpret_cast<const h8*>(reinterpret_cast<const _Float16*>(a.R) + z * a.sR + m * a.ldr + nb);
+                const h8* rp = reinterpret_cast<const h8*>(reinterpret_cast<const _Float16*>(a.R) + sh.z * a.sR + m * a.ldr + nb);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {       // acc + bias is rounded to the stream type BEFORE the residual joins it (and the
                     const h8 r8 = rp[q];            // sum is rounded again): what the 256 x 256 epilogue does in its 16-bit row layout
@@ -204,21 +246,14 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {
                     for (int e = 0; e < 8; ++e) v[q * 8 + e] = (float)(_Float16)v[q * 8 + e] + (float)r8[e];
                 }
             } else {
-                const float4* rp = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.R) + z * a.sR + m * a.ldr + nb);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 r4 = rp[q];
-                    v[q * 4 + 0] += r4.x; v[q * 4 + 1] += r4.y; v[q * 4 + 2] += r4.z; v[q * 4 + 3] += r4.w;
-                }
+                sh.add_res_f32(a, m, v);
             }
         }
-        if constexpr (OUT_F32) {
-            float4* cp = reinterpret_cast<float4*>(reinterpret_cast<float*>(a.C) + z * a.sC + m * a.ldc + nb);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) cp[q] = make_float4(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]);
+        if constexpr (OUT == 1) {
+            sh.store_f32(a, m, v);
         } else {
             using CT = typename std::conditional<OUT == 2, _Float16, T>::type;
-            u32x4* cp = reinterpret_cast<u32x4*>(reinterpret_cast<CT*>(a.C) + z * a.sC + m * a.ldc + nb);
+            u32x4* cp = reinterpret_cast<u32x4*>(reinterpret_cast<CT*>(a.C) + sh.z * a.sC + m * a.ldc + nb);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 u32x4 o;
@@ -241,84 +276,24 @@ template <bool OSPL>
 __global__ __launch_bounds__(256, 2) void gemm_split8_kernel(const GemmArgs a) {
     using X8 = f16x8;
     __shared__ __attribute__((aligned(16))) char smem[4 * kTileBytes];  // [buf][A|W]
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave & 1, wn = wave >> 1;
-    const int r15 = lane & 15, g = lane >> 4;
-    const int nblk = gridDim.x;
-    int id = xcd_remap(blockIdx.x, nblk);
-    const int per_batch = a.tiles_m * a.tiles_n;
-    const int z = id / per_batch;
-    id -= z * per_batch;
-    const int tile_m = id / a.tiles_n, tile_n = id - tile_m * a.tiles_n;
-    const int64_t m0 = (int64_t)tile_m * BM;
-    const int n0 = tile_n * BN;
-    const _Float16* A = reinterpret_cast<const _Float16*>(a.A) + z * a.sA;
-    const _Float16* W = reinterpret_cast<const _Float16*>(a.W) + z * a.sW;
-    const int srow = lane >> 3;
-    const int schunk = (lane & 7) ^ srow;
-    const _Float16* a_src[4];
-    const _Float16* w_src[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int lrow = (wave * 4 + j) * 8 + srow;
-        int64_t gm = m0 + lrow;
-        gm = gm < a.M ? gm : a.M - 1;
-        a_src[j] = A + gm * a.lda + schunk * 8;
-        const int perm = (lrow & 64) + ((lrow & 15) >> 2) * 16 + ((lrow >> 4) & 3) * 4 + (lrow & 3);
-        int gn = n0 + perm;
-        gn = gn < a.N ? gn : a.N - 1;
-        w_src[j] = W + (int64_t)gn * a.ldw + schunk * 8;
-    }
-    auto stage = [&](int kt, int buf) {
-        char* base = smem + buf * 2 * kTileBytes + wave * 4096;
-        const int koff = kt * 64;                                   // 128 bytes per K-tile whatever it holds
-#pragma unroll
-        for (int j = 0; j < 4; ++j) __builtin_amdgcn_global_load_lds((gptr_t)(a_src[j] + koff), (lptr_t)(base + j * 1024), 16, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) __builtin_amdgcn_global_load_lds((gptr_t)(w_src[j] + koff), (lptr_t)(base + kTileBytes + j * 1024), 16, 0, 0);
-    };
+    const Shell128<_Float16> sh(a);
     f32x4 acc[4][4];
-    {
-        const int nb_ = n0 + wn * 64 + g * 16;
-        float bias_[16];
-        if (a.bias != nullptr && nb_ + 16 <= a.N) {
-            const float4* bp = reinterpret_cast<const float4*>(a.bias + z * a.sBias + nb_);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 b4 = bp[q];
-                bias_[q * 4 + 0] = b4.x; bias_[q * 4 + 1] = b4.y; bias_[q * 4 + 2] = b4.z; bias_[q * 4 + 3] = b4.w;
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) bias_[q] = 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{bias_[j * 4 + 0], bias_[j * 4 + 1], bias_[j * 4 + 2], bias_[j * 4 + 3]};
-    }
-    const int a_row_off = (wm * 64 + r15) * 128;
-    const int w_row_off = (wn * 64 + r15) * 128;
-    const int swz = r15 & 7;
-    const int c0 = ((0 + g) ^ swz) << 4, c1 = ((4 + g) ^ swz) << 4;
+    sh.init_acc(a, acc);
+
+    const int c0 = sh.chunk_off(0), c1 = sh.chunk_off(4);
     const int nk = a.K >> 6;
     const int k_seg2 = a.k16 + (a.k16 >> 1);
-    stage(0, 0);
+    sh.stage(smem, 0, 0);
     for (int kt = 0; kt < nk; ++kt) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (explicit: see gemm_kernel)
-        __syncthreads();
-        if (kt + 1 < nk) stage(kt + 1, (kt + 1) & 1);
-        const char* As = smem + (kt & 1) * 2 * kTileBytes;
+        const char* As = sh.next_tile(smem, kt, nk);
         const char* Ws = As + kTileBytes;
         X8 af[4][2], wf[4][2];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            af[i][0] = *reinterpret_cast<const X8*>(As + a_row_off + i * 2048 + c0);
-            af[i][1] = *reinterpret_cast<const X8*>(As + a_row_off + i * 2048 + c1);
-            wf[i][0] = *reinterpret_cast<const X8*>(Ws + w_row_off + i * 2048 + c0);
-            wf[i][1] = *reinterpret_cast<const X8*>(Ws + w_row_off + i * 2048 + c1);
+            af[i][0] = *reinterpret_cast<const X8*>(As + sh.a_row_off() + i * 2048 + c0);
+            af[i][1] = *reinterpret_cast<const X8*>(As + sh.a_row_off() + i * 2048 + c1);
+            wf[i][0] = *reinterpret_cast<const X8*>(Ws + sh.w_row_off() + i * 2048 + c0);
+            wf[i][1] = *reinterpret_cast<const X8*>(Ws + sh.w_row_off() + i * 2048 + c1);
         }
         if (kt < a.k16) {
 #pragma unroll
@@ -342,46 +317,22 @@ __global__ __launch_bounds__(256, 2) void gemm_split8_kernel(const GemmArgs a) {
                     acc[mi][ni] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w8[ni], a8[mi], acc[mi][ni], 0, 0, 0, sc_w, 0, sc_a);
         }
     }
-    const int nb = n0 + wn * 64 + g * 16;
+
+    const int nb = sh.nb();
     if (nb + 16 > a.N) return;
     const bool has_res = a.R != nullptr;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
-        const int64_t m = m0 + wm * 64 + mi * 16 + r15;
+        const int64_t m = sh.row(mi);
         if (m >= a.M) continue;
         float v[16];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) v[ni * 4 + jj] = acc[mi][ni][jj];
-        if (a.act == CIR_ACT_GELU) {
-#pragma unroll
-            for (int q = 0; q < 16; q += 8) {      // the 256 x 256 kernel's packed evaluation: the same operations, the same bits
-                float w8[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) w8[e] = v[q + e];
-                gelu_erf_as8(w8);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[q + e] = w8[e];
-            }
-        } else if (a.act == CIR_ACT_RELU) {
-#pragma unroll
-            for (int q = 0; q < 16; ++q) v[q] = fmaxf(v[q], 0.f);
-        }
+        sh.unpack(acc[mi], v);
+        act16<true>(a.act, v);
         if constexpr (!OSPL) {
-            if (has_res) {
-                const float4* rp = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.R) + z * a.sR + m * a.ldr + nb);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float4 r4 = rp[q];
-                    v[q * 4 + 0] += r4.x; v[q * 4 + 1] += r4.y; v[q * 4 + 2] += r4.z; v[q * 4 + 3] += r4.w;
-                }
-            }
-            float4* cp = reinterpret_cast<float4*>(reinterpret_cast<float*>(a.C) + z * a.sC + m * a.ldc + nb);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) cp[q] = make_float4(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]);
+            if (has_res) sh.add_res_f32(a, m, v);
+            sh.store_f32(a, m, v);
         } else {
-            char* row = reinterpret_cast<char*>(a.C) + z * a.sC + m * a.ldc;       // bytes
+            char* row = reinterpret_cast<char*>(a.C) + sh.z * a.sC + m * a.ldc;       // bytes
             const float q0[4] = {v[0], v[1], v[2], v[3]}, q1[4] = {v[4], v[5], v[6], v[7]}, q2[4] = {v[8], v[9], v[10], v[11]}, q3[4] = {v[12], v[13], v[14], v[15]};
             const Split4 s0 = split8_x4(q0), s1 = split8_x4(q1), s2 = split8_x4(q2), s3 = split8_x4(q3);
             const u32x4 h0 = {s0.h01, s0.h23, s1.h01, s1.h23}, h1 = {s2.h01, s2.h23, s3.h01, s3.h23};
@@ -397,6 +348,33 @@ __global__ __launch_bounds__(256, 2) void gemm_split8_kernel(const GemmArgs a) {
 }  // namespace cir
 
 static inline int e8m0_word(int exp2) { const int b = (127 + exp2) & 0xff; return b * 0x01010101; }
+
+// The argument block of one launch (operand leading dimensions / strides in elements of the operand pointer type) with the 128 x 128
+// tile counts; the split8 / LayerNorm fields keep their defaults.  CIR_ESHAPE when the 128-tile grid does not fit an int.
+static int fill_gemm_args(cir::GemmArgs& a, const void* A, int64_t lda, int64_t sA, const void* W, int64_t ldw, int64_t sW, const float* bias,
+                          int64_t sBias, const void* R, int64_t ldr, int64_t sR, void* C, int64_t ldc, int64_t sC, int64_t M, int N, int K,
+                          int batch, int act) {
+    a.A = A; a.lda = lda; a.sA = sA;
+    a.W = W; a.ldw = ldw; a.sW = sW;
+    a.bias = bias; a.sBias = sBias;
+    a.R = R; a.ldr = ldr; a.sR = sR;
+    a.C = C; a.ldc = ldc; a.sC = sC;
+    a.M = M; a.N = N; a.K = K; a.batch = batch; a.act = act; a.group_w = 1; a.dbg = 0;
+    a.tiles_m = (int)((M + cir::BM - 1) / cir::BM);
+    a.tiles_n = (N + cir::BN - 1) / cir::BN;
+    return (int64_t)a.tiles_m * a.tiles_n * batch > 0x7fffffff ? CIR_ESHAPE : CIR_OK;
+}
+
+// Tile choice: the 256x256 8-phase kernel needs about a full wave of workgroups (256 CUs) to pay; small problems keep the 128x128
+// kernel (more, smaller tiles).  cir_set_tuning(CIR_TUNE_GEMM_TILE, 128|256) forces one - 256 only where the 256 kernel can take the
+// problem: `can256` (the caller's per-path condition) and tile-relative 32-bit operand offsets (leading dimensions < 2^21).
+static int gemm_tile(const cir::GemmArgs& a, bool can256) {
+    const int64_t nblk256 = ((a.M + 255) / 256) * ((a.N + 255) / 256) * a.batch;
+    bool use256 = a.N >= 256 && nblk256 >= 192;
+    if (cir::g_tune[CIR_TUNE_GEMM_TILE] == 128) use256 = false;
+    else if (cir::g_tune[CIR_TUNE_GEMM_TILE] == 256) use256 = true;
+    return use256 && can256 && a.lda < (1 << 21) && a.ldw < (1 << 21) ? 256 : 128;
+}
 
 extern "C" int cir_gemm_split8(const void* A, int64_t lda_bytes, int64_t strideA_bytes, const void* W, int64_t ldw_bytes, int64_t strideW_bytes,
                                const float* bias, int64_t strideBias, const float* residual, int64_t ldr, int64_t strideR,
@@ -417,30 +395,18 @@ extern "C" int cir_gemm_split8(const void* A, int64_t lda_bytes, int64_t strideA
     if (bias && (!cir_aligned16(bias) || strideBias % 4)) return CIR_EALIGN;
     if (residual && (!cir_aligned16(residual) || ldr % 4 || strideR % 4)) return CIR_EALIGN;
     GemmArgs a;
-    a.A = A; a.lda = lda_bytes / 2; a.sA = strideA_bytes / 2;
-    a.W = W; a.ldw = ldw_bytes / 2; a.sW = strideW_bytes / 2;
-    a.bias = bias; a.sBias = strideBias;
-    a.R = residual; a.ldr = ldr; a.sR = strideR;
-    a.C = C; a.ldc = ldc; a.sC = strideC;
-    a.M = M; a.N = N; a.K = 2 * K; a.batch = batch; a.act = act; a.group_w = 1; a.dbg = 0;
+    if (fill_gemm_args(a, A, lda_bytes / 2, strideA_bytes / 2, W, ldw_bytes / 2, strideW_bytes / 2, bias, strideBias, residual, ldr, strideR,
+                       C, ldc, strideC, M, N, 2 * K, batch, act) != CIR_OK) return CIR_ESHAPE;
     a.k16 = K / 64;
     a.sc_a1 = e8m0_word(-kSplitLoExp); a.sc_w1 = e8m0_word(-w_exp_hi);
     a.sc_a2 = e8m0_word(0); a.sc_w2 = e8m0_word(-w_exp_lo);
     a.n_logical = N;
-    a.tiles_m = (int)((M + BM - 1) / BM);
-    a.tiles_n = (N + BN - 1) / BN;
-    const int64_t nblk = (int64_t)a.tiles_m * a.tiles_n * batch;
-    if (nblk > 0x7fffffff) return CIR_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int64_t nblk256 = ((M + 255) / 256) * ((N + 255) / 256) * batch;
-    bool use256 = N >= 256 && nblk256 >= 192 && a.lda < (1 << 21) && a.ldw < (1 << 21);
-    if (g_tune[CIR_TUNE_GEMM_TILE] == 128) use256 = false;
-    else if (g_tune[CIR_TUNE_GEMM_TILE] == 256) use256 = a.lda < (1 << 21) && a.ldw < (1 << 21);
-    if (use256) {
+    if (gemm_tile(a, true) == 256) {
         launch_gemm256_split8(a, out_split, s);
         CIR_LAUNCH_RESULT();
     }
-    dim3 grid((unsigned)nblk), block(256);
+    dim3 grid((unsigned)(a.tiles_m * a.tiles_n * batch)), block(256);
     if (out_split) hipLaunchKernelGGL((gemm_split8_kernel<true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((gemm_split8_kernel<false>), grid, block, 0, s, a);
     CIR_LAUNCH_RESULT();
@@ -463,17 +429,9 @@ extern "C" int cir_gemm_bias_act(const void* A, int64_t lda, int64_t strideA, co
         if (bias && (!cir_aligned16(bias) || strideBias % 4)) return CIR_EALIGN;
         if (residual && (!cir_aligned16(residual) || ldr % 4 || strideR % 4)) return CIR_EALIGN;
         GemmArgs a;
-        a.A = A; a.lda = lda; a.sA = strideA;
-        a.W = W; a.ldw = ldw; a.sW = strideW;
-        a.bias = bias; a.sBias = strideBias;
-        a.R = residual; a.ldr = ldr; a.sR = strideR;
-        a.C = C; a.ldc = ldc; a.sC = strideC;
-        a.M = M; a.N = N; a.K = K; a.batch = batch; a.act = act; a.group_w = 1; a.dbg = 0;
-        a.tiles_m = (int)((M + BM - 1) / BM);
-        a.tiles_n = (N + BN - 1) / BN;
-        const int64_t nblk = (int64_t)a.tiles_m * a.tiles_n * batch;
-        if (nblk > 0x7fffffff) return CIR_ESHAPE;
-        hipLaunchKernelGGL((gemm_kernel<float, 1>), dim3((unsigned)nblk), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+        if (fill_gemm_args(a, A, lda, strideA, W, ldw, strideW, bias, strideBias, residual, ldr, strideR, C, ldc, strideC, M, N, K, batch, act) != CIR_OK)
+            return CIR_ESHAPE;
+        hipLaunchKernelGGL((gemm_kernel<float, 1>), dim3((unsigned)(a.tiles_m * a.tiles_n * batch)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
         CIR_LAUNCH_RESULT();
     }
     if (K % BK != 0 || N % 16 != 0) return CIR_ESHAPE;
@@ -494,34 +452,19 @@ extern "C" int cir_gemm_bias_act(const void* A, int64_t lda, int64_t strideA, co
     if (residual && (!cir_aligned16(residual) || ldr % res_elems_per16 || strideR % res_elems_per16)) return CIR_EALIGN;
 
     GemmArgs a;
-    a.A = A; a.lda = lda; a.sA = strideA;
-    a.W = W; a.ldw = ldw; a.sW = strideW;
-    a.bias = bias; a.sBias = strideBias;
-    a.R = residual; a.ldr = ldr; a.sR = strideR;
-    a.C = C; a.ldc = ldc; a.sC = strideC;
-    a.M = M; a.N = N; a.K = K; a.batch = batch; a.act = act; a.group_w = 1;
-    a.tiles_m = (int)((M + BM - 1) / BM);
-    a.tiles_n = (N + BN - 1) / BN;
-    const int64_t nblk = (int64_t)a.tiles_m * a.tiles_n * batch;
-    if (nblk > 0x7fffffff) return CIR_ESHAPE;
+    if (fill_gemm_args(a, A, lda, strideA, W, ldw, strideW, bias, strideBias, residual, ldr, strideR, C, ldc, strideC, M, N, K, batch, act) != CIR_OK)
+        return CIR_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // epilogue kind: 1 = fp32 C (fp32 residual), 2 = fp16 stream C with an fp16 residual or from bf16 operands,
     // 0 = C in the operand type (an fp32 residual is then served by the 128 x 128 kernel only)
     const bool stream16 = out_dtype == CIR_F16 && (in_dtype != CIR_F16 || (residual && res_dtype == CIR_F16));
     const int out_kind = out_dtype == CIR_F32 ? 1 : (stream16 ? 2 : 0);
-    // Tile choice: the 256x256 8-phase kernel needs about a full wave of workgroups (256 CUs) to pay;
-    // small problems keep the 128x128 kernel (more, smaller tiles).  cir_set_tuning(CIR_TUNE_GEMM_TILE, 128|256) forces one.
-    const int64_t nblk256 = ((M + 255) / 256) * ((N + 255) / 256) * batch;
-    // (the 256 kernel adds the residual in the row layout of its fp32-layout epilogues: linear epilogues only; 32-bit operand offsets)
-    bool use256 = N >= 256 && nblk256 >= 192;
-    const bool can256 = !(residual && (act != CIR_ACT_NONE || out_kind == 0)) && K % 128 == 0 && lda < (1 << 21) && ldw < (1 << 21);   // K-tile pairs; tile-relative 32-bit offsets
-    if (g_tune[CIR_TUNE_GEMM_TILE] == 128) use256 = false;
-    else if (g_tune[CIR_TUNE_GEMM_TILE] == 256) use256 = true;
-    if (use256 && can256) {
+    // (the 256 kernel adds the residual in the row layout of its fp32-layout epilogues: linear epilogues only; K-tile pairs)
+    if (gemm_tile(a, !(residual && (act != CIR_ACT_NONE || out_kind == 0)) && K % 128 == 0) == 256) {
         launch_gemm256(a, in_dtype, out_kind, s);
         CIR_LAUNCH_RESULT();
     }
-    dim3 grid((unsigned)nblk), block(256);
+    dim3 grid((unsigned)(a.tiles_m * a.tiles_n * batch)), block(256);
 #define CIR_LAUNCH128(TT) \
     do { if (out_kind == 1) hipLaunchKernelGGL((gemm_kernel<TT, 1>), grid, block, 0, s, a); \
          else if (out_kind == 2) hipLaunchKernelGGL((gemm_kernel<TT, 2>), grid, block, 0, s, a); \

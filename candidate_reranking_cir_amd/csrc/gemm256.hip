@@ -825,14 +825,9 @@ static int persistent_grid() {
     return cus;
 }
 
-void launch_gemm256(const GemmArgs& a_in, int in_dtype, int out_kind, hipStream_t s) {
-    // out_kind: 0 = 16-bit C in the operand type, 1 = fp32 C (and R), 2 = fp16 residual-stream C (and R);
-    // 3 = LayerNorm folded in (fp16 rows in, fp16 C; a.colsum / a.ln_eps set; act NONE or GELU)
-    GemmArgs a = a_in;
+// The raster plan of one launch: 256 x 256 tile counts and the column-group width into `a`; returns the persistent grid.
+static dim3 plan256(GemmArgs& a) {
     a.dbg = 0;
-#ifdef CIR_GEMM_STAMPS
-    if (const char* e = getenv("CIR_DBG")) a.dbg = (int)strtol(e, nullptr, 0);
-#endif
     a.tiles_m = (int)((a.M + T256 - 1) / T256);
     a.tiles_n = (a.N + T256 - 1) / T256;
     const int64_t ntiles = (int64_t)a.tiles_m * a.tiles_n * a.batch;
@@ -850,7 +845,17 @@ void launch_gemm256(const GemmArgs& a_in, int in_dtype, int out_kind, hipStream_
     if (const int v = g_tune[CIR_TUNE_GEMM_GROUP_W]; v > 0) gw = v < a.tiles_n ? v : a.tiles_n;
     a.group_w = gw;
     const int64_t g = persistent_grid();
-    dim3 grid((unsigned)(ntiles < g ? ntiles : g)), block(512);
+    return dim3((unsigned)(ntiles < g ? ntiles : g));
+}
+
+void launch_gemm256(const GemmArgs& a_in, int in_dtype, int out_kind, hipStream_t s) {
+    // out_kind: 0 = 16-bit C in the operand type, 1 = fp32 C (and R), 2 = fp16 residual-stream C (and R);
+    // 3 = LayerNorm folded in (fp16 rows in, fp16 C; a.colsum / a.ln_eps set; act NONE or GELU)
+    GemmArgs a = a_in;
+    const dim3 grid = plan256(a), block(512);
+#ifdef CIR_GEMM_STAMPS
+    if (const char* e = getenv("CIR_DBG")) a.dbg = (int)strtol(e, nullptr, 0);
+#endif
     const bool res = a.R != nullptr;
 #define CIR_LAUNCH256(...) hipLaunchKernelGGL((gemm256_kernel<__VA_ARGS__>), grid, block, 0, s, a)
     if (out_kind == 3) {
@@ -878,20 +883,7 @@ void launch_gemm256(const GemmArgs& a_in, int in_dtype, int out_kind, hipStream_
 
 void launch_gemm256_split8(const GemmArgs& a_in, int out_split, hipStream_t s) {
     GemmArgs a = a_in;
-    a.dbg = 0;
-    a.tiles_m = (int)((a.M + T256 - 1) / T256);
-    a.tiles_n = (a.N + T256 - 1) / T256;
-    const int64_t ntiles = (int64_t)a.tiles_m * a.tiles_n * a.batch;
-    int gw = 1;
-    float best = 1e30f;
-    for (int d = 1; d <= a.tiles_n && d <= 12; ++d) {
-        const float cost = d + 32.0f / d + (a.tiles_n % d ? 1.5f : 0.f);
-        if (cost < best) { best = cost; gw = d; }
-    }
-    if (const int v = g_tune[CIR_TUNE_GEMM_GROUP_W]; v > 0) gw = v < a.tiles_n ? v : a.tiles_n;
-    a.group_w = gw;
-    const int64_t g = persistent_grid();
-    dim3 grid((unsigned)(ntiles < g ? ntiles : g)), block(512);
+    const dim3 grid = plan256(a), block(512);
 #define CIR_LAUNCH256(...) hipLaunchKernelGGL((gemm256_kernel<__VA_ARGS__>), grid, block, 0, s, a)
     if (out_split) {
         if (a.act == CIR_ACT_GELU) CIR_LAUNCH256(_Float16, true, false, float, CIR_ACT_GELU, false, true, true);

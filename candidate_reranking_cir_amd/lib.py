@@ -97,6 +97,7 @@ SIGNATURES = {
 }
 
 _lib = None
+TUNING = {}           # knob -> value of every set_tuning call (ops.gemm_kernel_name reports the tile the library was told to use)
 PARAM_EPOCH = [0]     # moved by every cir_adamw_step launch and torch.optim step: a ViT training forward's backward compares it (train_vit.py)
 
 
@@ -133,6 +134,7 @@ def load() -> ctypes.CDLL:
 def set_tuning(knob: int, value: int):
     """Kernel-selection override (include/cirrank.h: cir_set_tuning); 0 restores the automatic choice."""
     check(load().cir_set_tuning(knob, value), "cir_set_tuning")
+    TUNING[knob] = value
 
 
 def check(code: int, what: str):

@@ -21,10 +21,16 @@ PROFILE_ATTN = None
 
 
 def gemm_kernel_name(m: int, n: int, k: int, nb: int, has_residual: bool, act: int, out_dtype, in_dtype: torch.dtype, tile: int = 0,
-                     res_dtype=None) -> str:
-    """Which kernel instantiation cir_gemm_bias_act launches for a shape (mirror of the dispatch in csrc/gemm.hip; for
-    reporting only - the library decides).  `out_dtype`: torch dtype (or True / False = fp32 / operand type)."""
-    if in_dtype == torch.float32:
+                     res_dtype=None, lda: int = 0, ldw: int = 0, form: str = "gemm") -> str:
+    """Which kernel instantiation the GEMM family launches for a shape: the dispatch rule of csrc/gemm.hip (gemm_tile) stated once, for
+    reporting only - the library decides.  `form`: "gemm" = cir_gemm_bias_act, "ln" = cir_gemm_ln_bias_act, "split8" = cir_gemm_split8
+    (m, n, k logical; `in_dtype` unused).  `out_dtype`: torch dtype (or True / False = fp32 / operand type; torch.uint8 = split8 rows out).
+    `lda` / `ldw`: leading dimensions in the library's units (operand elements; 2 bytes for split8 rows); `tile`: the CIR_TUNE_GEMM_TILE
+    override in force (forced 256 still falls back to 128 where the 256 kernel cannot take the problem)."""
+    if form == "ln":                                   # the LayerNorm-folded GEMM exists on the 256 x 256 tile only
+        return f"cir::gemm256_kernel<_Float16,false,false,float,{act},true>"
+    split8 = form == "split8"
+    if in_dtype == torch.float32 and not split8:
         return "cir::gemm_kernel<float,1>"
     if isinstance(out_dtype, bool):
         out_dtype = torch.float32 if out_dtype else in_dtype
@@ -33,19 +39,29 @@ def gemm_kernel_name(m: int, n: int, k: int, nb: int, has_residual: bool, act: i
     kind = 1 if out_dtype == torch.float32 else (2 if stream16 else 0)
     nblk256 = -(-m // 256) * -(-n // 256) * nb
     use256 = n >= 256 and nblk256 >= 192
-    can256 = not (has_residual and (act != ACT_NONE or kind == 0)) and k % 128 == 0
+    can256 = split8 or (not (has_residual and (act != ACT_NONE or kind == 0)) and k % 128 == 0)
     if tile == 128:
         use256 = False
     elif tile == 256:
         use256 = True
-    if use256 and can256:
-        name = f"cir::gemm256_kernel<{t},{'true' if kind == 1 else 'false'},{'true' if has_residual else 'false'}"
-        if kind == 2:       # fp16 residual-stream C: the activation is a template constant when there is none
-            return name + (",_Float16,0>" if act == ACT_NONE else ",_Float16>")
-        if kind == 0 and act in (ACT_NONE, ACT_GELU):
-            return name + f",float,{act}>"
-        return name + ">"
-    return f"cir::gemm_kernel<{t},{kind}>"
+    if not (use256 and can256 and lda < (1 << 21) and ldw < (1 << 21)):
+        return "cir::gemm_split8_kernel" if split8 else f"cir::gemm_kernel<{t},{kind}>"
+    if split8:
+        return "cir::gemm256_kernel<split8%s>" % (",split8-out" if out_dtype == torch.uint8 else (",residual" if has_residual else ""))
+    name = f"cir::gemm256_kernel<{t},{'true' if kind == 1 else 'false'},{'true' if has_residual else 'false'}"
+    if kind == 2:       # fp16 residual-stream C: the activation is a template constant when there is none
+        return name + (",_Float16,0>" if act == ACT_NONE else ",_Float16>")
+    if kind == 0 and act in (ACT_NONE, ACT_GELU):
+        return name + f",float,{act}>"
+    return name + ">"
+
+
+def _events():
+    """A HIP event pair for timing one launch on the current stream (bench.py's PROFILE_* lists), the first one recorded.  Call it only
+    with profiling on: a launch pays one `is None` test per list otherwise."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0, e1
 
 
 def _stream() -> int:
@@ -62,6 +78,45 @@ def _need_cuda(*tensors):
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
+
+
+def _rows2d(x: torch.Tensor) -> torch.Tensor:
+    """(..., K) with contiguous rows -> (rows, K) with ONE row stride: a view where one exists, a copy otherwise."""
+    k = x.shape[-1]
+    if x.dim() == 2:
+        return x
+    if x.is_contiguous():
+        return x.reshape(-1, k)
+    if x.dim() == 3 and x.stride(0) == x.shape[1] * x.stride(1):   # (B, M, K) views with a uniform row stride (e.g. the CLS rows of a (.., L, D) tensor)
+        return x.as_strided((x.shape[0] * x.shape[1], k), (x.stride(1), 1))
+    return x.contiguous().view(-1, k)
+
+
+def _gemm_views(a: torch.Tensor, w: torch.Tensor, bias, residual, out, out_dtype: torch.dtype, out_per_n: int = 1):
+    """What `gemm` and `_gemm_split8` marshal alike: a (M,K') / (B,M,K') and w (N,K') / (B,N,K') as 3-D views, `out` (allocated when None)
+    with rows of `out_per_n` N elements of `out_dtype`, the bias batch stride and the residual's row / batch strides.
+    Returns (a3, w3, out, o3, B, M, N, K', bias stride, ldr, residual stride)."""
+    batched = a.dim() == 3
+    a3 = a if batched else a.unsqueeze(0)
+    w3 = w if w.dim() == 3 else w.unsqueeze(0)
+    nb, m, kk = a3.shape
+    wb, n, wk = w3.shape
+    out_cols = n * out_per_n
+    assert wb == nb and wk == kk and a3.stride(2) == 1 and w3.stride(2) == 1
+    if out is None:
+        out = torch.empty((nb, m, out_cols) if batched else (m, out_cols), dtype=out_dtype, device=a.device)
+    o3 = out if out.dim() == 3 else out.unsqueeze(0)
+    assert o3.shape == (nb, m, out_cols) and o3.stride(2) == 1 and o3.dtype == out_dtype
+    sb = 0
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.stride(-1) == 1
+        sb = bias.stride(0) if bias.dim() == 2 else 0
+    ldr = sr = 0
+    if residual is not None:
+        r3 = residual if residual.dim() == 3 else residual.unsqueeze(0)
+        assert r3.shape == (nb, m, n) and r3.stride(2) == 1
+        ldr, sr = r3.stride(1), r3.stride(0)
+    return a3, w3, out, o3, nb, m, n, kk, sb, ldr, sr
 
 
 class SplitOperand:
@@ -89,12 +144,7 @@ def split16(x: torch.Tensor, act: int = ACT_NONE) -> SplitOperand:
     _need_cuda(x)
     assert x.dtype == torch.float32 and x.stride(-1) == 1
     k = x.shape[-1]
-    x2 = x if x.dim() == 2 else x.reshape(-1, k) if x.is_contiguous() else None
-    if x2 is None:                                   # (B, M, K) views with a uniform row stride (e.g. the CLS rows of a (.., L, D) tensor)
-        if x.dim() == 3 and x.stride(0) == x.shape[1] * x.stride(1):
-            x2 = x.as_strided((x.shape[0] * x.shape[1], k), (x.stride(1), 1))
-        else:
-            x2 = x.contiguous().view(-1, k)
+    x2 = _rows2d(x)
     cat = torch.empty(x.shape[:-1] + (3 * k,), dtype=torch.float16, device=x.device)
     p = cat.data_ptr()
     _lib.check(_lib.load().cir_split16(x2.data_ptr(), x2.stride(0), p, p + 2 * k, p + 4 * k, 3 * k, x2.shape[0], k, act, _stream()), "cir_split16")
@@ -157,12 +207,7 @@ def split8(x: torch.Tensor, act: int = ACT_NONE, out: Optional[torch.Tensor] = N
     _need_cuda(x, out)
     assert x.dtype == torch.float32 and x.stride(-1) == 1
     k = x.shape[-1]
-    x2 = x if x.dim() == 2 else x.reshape(-1, k) if x.is_contiguous() else None
-    if x2 is None:
-        if x.dim() == 3 and x.stride(0) == x.shape[1] * x.stride(1):
-            x2 = x.as_strided((x.shape[0] * x.shape[1], k), (x.stride(1), 1))
-        else:
-            x2 = x.contiguous().view(-1, k)
+    x2 = _rows2d(x)
     if out is None:
         out = torch.empty(x.shape[:-1] + (4 * k,), dtype=torch.uint8, device=x.device)
     assert out.is_contiguous() and out.dtype == torch.uint8 and out.numel() == x2.shape[0] * 4 * k
@@ -198,48 +243,22 @@ def _gemm_split8(a, wpack, bias, residual, act, out):
     rows_w, e1, e2 = wpack
     sa = a if isinstance(a, Split8Operand) else split8(a)
     _need_cuda(sa.rows, rows_w, bias, residual, out)
-    k = sa.k
-    batched = sa.rows.dim() == 3
-    a3 = sa.rows if batched else sa.rows.unsqueeze(0)
-    w3 = rows_w if rows_w.dim() == 3 else rows_w.unsqueeze(0)
-    nb, m, _ = a3.shape
-    n = w3.shape[1]
-    assert w3.shape[0] == nb and w3.shape[2] == 4 * k and a3.stride(2) == 1 and w3.stride(2) == 1
     assert act == ACT_NONE or residual is None, "activation and residual do not meet on this path"
+    assert residual is None or residual.dtype == torch.float32
     out_split = act == ACT_GELU
-    if out_split:
-        assert out is None
-        res = torch.empty((nb, m, 4 * n) if batched else (m, 4 * n), dtype=torch.uint8, device=a3.device)
-        o3 = res if batched else res.unsqueeze(0)
-        ldc, sc = o3.stride(1), o3.stride(0)
-    else:
-        if out is None:
-            out = torch.empty((nb, m, n) if batched else (m, n), dtype=torch.float32, device=a3.device)
-        res = out
-        o3 = out if out.dim() == 3 else out.unsqueeze(0)
-        assert o3.shape == (nb, m, n) and o3.stride(2) == 1 and o3.dtype == torch.float32
-        ldc, sc = o3.stride(1), o3.stride(0)
-    sb = 0
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.stride(-1) == 1
-        sb = bias.stride(0) if bias.dim() == 2 else 0
-    ldr = sr = 0
-    if residual is not None:
-        r3 = residual if residual.dim() == 3 else residual.unsqueeze(0)
-        assert r3.shape == (nb, m, n) and r3.stride(2) == 1 and r3.dtype == torch.float32
-        ldr, sr = r3.stride(1), r3.stride(0)
-    if PROFILE_GEMM is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    assert out is None or not out_split
+    k = sa.k
+    a3, w3, res, o3, nb, m, n, _, sb, ldr, sr = _gemm_views(sa.rows, rows_w, bias, residual, out, *((torch.uint8, 4) if out_split else (torch.float32, 1)))
+    ev = _events() if PROFILE_GEMM is not None else None
     code = _lib.load().cir_gemm_split8(a3.data_ptr(), a3.stride(1), a3.stride(0), w3.data_ptr(), w3.stride(1), w3.stride(0), _ptr(bias), sb,
-                                       _ptr(residual), ldr, sr, o3.data_ptr(), ldc, sc, m, n, k, nb, act, int(out_split), e1, e2, _stream())
-    if PROFILE_GEMM is not None:
-        ev1.record()     # USEFUL flops (2 m n k): the two correction products are this path's overhead, not work done
+                                       _ptr(residual), ldr, sr, o3.data_ptr(), o3.stride(1), o3.stride(0), m, n, k, nb, act, int(out_split),
+                                       e1, e2, _stream())
+    if ev is not None:
+        ev[1].record()     # USEFUL flops (2 m n k): the two correction products are this path's overhead, not work done
         alg_bytes = nb * ((m * k + n * k) * 4 + m * n * 4 + (m * n * 4 if residual is not None else 0) + (n * 4 if bias is not None else 0))
-        nblk256 = -(-m // 256) * -(-n // 256) * nb
-        name = "cir::gemm256_kernel<split8%s>" % (",split8-out" if out_split else (",residual" if residual is not None else "")) \
-            if (n >= 256 and nblk256 >= 192) else "cir::gemm_split8_kernel"
-        PROFILE_GEMM.append((2.0 * nb * m * n * k, ev0, ev1, float(alg_bytes), name))
+        PROFILE_GEMM.append((2.0 * nb * m * n * k, *ev, float(alg_bytes),
+                             gemm_kernel_name(m, n, k, nb, residual is not None, act, o3.dtype, torch.float32, _lib.TUNING.get(_lib.TUNE_GEMM_TILE, 0),
+                                              lda=a3.stride(1) // 2, ldw=w3.stride(1) // 2, form="split8")))
     _lib.check(code, "cir_gemm_split8")
     return Split8Operand(res, n) if out_split else res
 
@@ -257,46 +276,26 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         assert out_dtype in (None, torch.float32) and getattr(w, "_split3", None) is not None
         return _gemm_split3(a, w._split3, bias, residual, act, out)
     _need_cuda(a, w, bias, residual, out)
-    batched = a.dim() == 3
-    if not batched:
-        a3, w3 = a.unsqueeze(0), w.unsqueeze(0)
-    else:
-        a3, w3 = a, w
-    nb, m, k = a3.shape
-    n = w3.shape[1]
-    assert w3.shape[0] == nb and w3.shape[2] == k and a3.stride(2) == 1 and w3.stride(2) == 1
-    assert w3.dtype == a3.dtype, "operands of one type (16-bit, or fp32 for the exact mode)"
+    assert w.dtype == a.dtype, "operands of one type (16-bit, or fp32 for the exact mode)"
     out_dtype = out_dtype or a.dtype
-    if out is None:
-        out = torch.empty((nb, m, n) if batched else (m, n), dtype=out_dtype, device=a.device)
-    o3 = out if out.dim() == 3 else out.unsqueeze(0)
-    assert o3.shape == (nb, m, n) and o3.stride(2) == 1 and o3.dtype == out_dtype
-    sb = 0
-    if bias is not None:
-        assert bias.dtype == torch.float32 and bias.stride(-1) == 1
-        sb = bias.stride(0) if bias.dim() == 2 else 0
-    ldr = sr = 0
     if residual is not None:
-        r3 = residual if residual.dim() == 3 else residual.unsqueeze(0)
-        assert r3.shape == (nb, m, n) and r3.stride(2) == 1
-        assert r3.dtype == torch.float32 or (r3.dtype == torch.float16 and out_dtype == torch.float16), "residual: fp32, or fp16 with an fp16 out"
-        assert not (out_dtype == torch.float16 and a.dtype != torch.float16 and r3.dtype != torch.float16), \
+        assert residual.dtype == torch.float32 or (residual.dtype == torch.float16 and out_dtype == torch.float16), \
+            "residual: fp32, or fp16 with an fp16 out"
+        assert not (out_dtype == torch.float16 and a.dtype != torch.float16 and residual.dtype != torch.float16), \
             "an fp16 out from bf16 operands (residual stream) takes an fp16 residual"
-        ldr, sr = r3.stride(1), r3.stride(0)
-    if PROFILE_GEMM is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    a3, w3, out, o3, nb, m, n, k, sb, ldr, sr = _gemm_views(a, w, bias, residual, out, out_dtype)
+    ev = _events() if PROFILE_GEMM is not None else None
     code = _lib.load().cir_gemm_bias_act(
         a3.data_ptr(), a3.stride(1), a3.stride(0), w3.data_ptr(), w3.stride(1), w3.stride(0),
         _ptr(bias), sb, _ptr(residual), _DT[residual.dtype] if residual is not None else CIR_F32, ldr, sr,
         o3.data_ptr(), o3.stride(1), o3.stride(0), m, n, k, nb, act, _DT[a.dtype], _DT[out_dtype], _stream())
-    if PROFILE_GEMM is not None:
-        ev1.record()
+    if ev is not None:
+        ev[1].record()
         alg_bytes = nb * ((m * k + n * k) * a.element_size() + m * n * o3.element_size()
                           + (m * n * residual.element_size() if residual is not None else 0) + (n * 4 if bias is not None else 0))
-        PROFILE_GEMM.append((2.0 * nb * m * n * k, ev0, ev1, float(alg_bytes),
-                             gemm_kernel_name(m, n, k, nb, residual is not None, act, out_dtype, a.dtype,
-                                              res_dtype=residual.dtype if residual is not None else None)))
+        PROFILE_GEMM.append((2.0 * nb * m * n * k, *ev, float(alg_bytes),
+                             gemm_kernel_name(m, n, k, nb, residual is not None, act, out_dtype, a.dtype, _lib.TUNING.get(_lib.TUNE_GEMM_TILE, 0),
+                                              residual.dtype if residual is not None else None, a3.stride(1), w3.stride(1))))
     _lib.check(code, "cir_gemm_bias_act")
     return out
 
@@ -323,17 +322,33 @@ def gemm_ln(x: torch.Tensor, wg: torch.Tensor, colsum: torch.Tensor, bias: torch
     if out is None:
         out = torch.empty((m, n), dtype=torch.float16, device=x.device)
     assert out.shape == (m, n) and out.dtype == torch.float16 and out.stride(1) == 1
-    if PROFILE_GEMM is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev = _events() if PROFILE_GEMM is not None else None
     code = _lib.load().cir_gemm_ln_bias_act(x.data_ptr(), x.stride(0), wg.data_ptr(), wg.stride(0), colsum.data_ptr(), bias.data_ptr(),
                                             out.data_ptr(), out.stride(0), m, n, k, float(eps), act, CIR_F16, _stream())
-    if PROFILE_GEMM is not None:
-        ev1.record()
-        PROFILE_GEMM.append((2.0 * m * n * k, ev0, ev1, float((m * k + n * k + m * n) * 2 + n * 8),
-                             f"cir::gemm256_kernel<_Float16,false,false,float,{act},true>"))
+    if ev is not None:
+        ev[1].record()
+        PROFILE_GEMM.append((2.0 * m * n * k, *ev, float((m * k + n * k + m * n) * 2 + n * 8),
+                             gemm_kernel_name(m, n, k, 1, False, act, torch.float16, torch.float16, form="ln")))
     _lib.check(code, "cir_gemm_ln_bias_act")
     return out
+
+
+def _ln_views(x: torch.Tensor, gamma: torch.Tensor, residual: Optional[torch.Tensor], dtypes):
+    """The broadcast marshalling `layernorm` and `layernorm_split8` share: x / residual (rows, cols) or (B, rows, cols) in one of `dtypes`,
+    gamma (cols) or (B, cols); a batch of one is broadcast with stride 0.
+    Returns (x3, nb, rows, cols, leading shape of the outputs, x batch stride, residual batch stride, gamma batch stride)."""
+    x3 = x if x.dim() == 3 else x.unsqueeze(0)
+    nb = max(x3.shape[0], gamma.shape[0] if gamma.dim() == 2 else 1, (residual.shape[0] if residual is not None and residual.dim() == 3 else 1))
+    rows, cols = x3.shape[1], x3.shape[2]
+    assert x3.dtype in dtypes and x3.stride(2) == 1 and x3.stride(1) == cols
+    sx = x3.stride(0) if x3.shape[0] > 1 else 0
+    sr = 0
+    if residual is not None:
+        r3 = residual if residual.dim() == 3 else residual.unsqueeze(0)
+        assert r3.dtype == x3.dtype and r3.stride(2) == 1 and r3.stride(1) == cols
+        sr = r3.stride(0) if r3.shape[0] > 1 else 0
+    sg = gamma.stride(0) if gamma.dim() == 2 else 0
+    return x3, nb, rows, cols, ((nb, rows) if (x.dim() == 3 or nb > 1) else (rows,)), sx, sr, sg
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, residual: Optional[torch.Tensor] = None,
@@ -345,24 +360,13 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     gamma/beta (cols) or (B, cols); x/residual may be batch-broadcast (stride 0) views.  `dtype16=None` skips the operand
     copy, `want32=False` the stream copy."""
     _need_cuda(x, gamma, beta, residual)
-    x3 = x if x.dim() == 3 else x.unsqueeze(0)
-    nb = max(x3.shape[0], gamma.shape[0] if gamma.dim() == 2 else 1, (residual.shape[0] if residual is not None and residual.dim() == 3 else 1))
-    rows, cols = x3.shape[1], x3.shape[2]
-    assert x3.dtype in (torch.float32, torch.float16) and x3.stride(2) == 1 and x3.stride(1) == cols
+    x3, nb, rows, cols, lead, sx, sr, sg = _ln_views(x, gamma, residual, (torch.float32, torch.float16))
     stream_dtype = stream_dtype or (out32.dtype if out32 is not None else x3.dtype)
     assert stream_dtype in (torch.float32, torch.float16)
-    shape = (nb, rows, cols) if (x.dim() == 3 or nb > 1) else (rows, cols)
     if out32 is None and want32:
-        out32 = torch.empty(shape, dtype=stream_dtype, device=x.device)
+        out32 = torch.empty(lead + (cols,), dtype=stream_dtype, device=x.device)
     if out16 is None and dtype16 is not None:
-        out16 = torch.empty(shape, dtype=dtype16, device=x.device)
-    sx = x3.stride(0) if x3.shape[0] > 1 else 0
-    sr = 0
-    if residual is not None:
-        r3 = residual if residual.dim() == 3 else residual.unsqueeze(0)
-        assert r3.dtype == x3.dtype and r3.stride(2) == 1 and r3.stride(1) == cols
-        sr = r3.stride(0) if r3.shape[0] > 1 else 0
-    sg = gamma.stride(0) if gamma.dim() == 2 else 0
+        out16 = torch.empty(lead + (cols,), dtype=dtype16, device=x.device)
     d16 = _DT[out16.dtype] if out16 is not None else CIR_BF16
     code = _lib.load().cir_layernorm(x3.data_ptr(), _DT[x3.dtype], sx, _ptr(residual), sr, gamma.data_ptr(), beta.data_ptr(), sg,
                                      _ptr(out32), _DT[out32.dtype] if out32 is not None else CIR_F32, _ptr(out16), rows * cols, rows, cols, nb,
@@ -376,20 +380,9 @@ def layernorm_split8(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, e
     """LayerNorm of fp32 stream rows -> (fp32 stream copy or None, Split8Operand of the same values): cir_layernorm_split8.  Shapes and
     broadcasting as `layernorm` (x / residual (rows, cols) or (B, rows, cols), gamma / beta (cols) or (B, cols))."""
     _need_cuda(x, gamma, beta, residual)
-    x3 = x if x.dim() == 3 else x.unsqueeze(0)
-    nb = max(x3.shape[0], gamma.shape[0] if gamma.dim() == 2 else 1, (residual.shape[0] if residual is not None and residual.dim() == 3 else 1))
-    rows, cols = x3.shape[1], x3.shape[2]
-    assert x3.dtype == torch.float32 and x3.stride(2) == 1 and x3.stride(1) == cols
-    shape = (nb, rows) if (x.dim() == 3 or nb > 1) else (rows,)
-    ys = torch.empty(shape + (cols,), dtype=torch.float32, device=x.device) if want_stream else None
-    sp = torch.empty(shape + (4 * cols,), dtype=torch.uint8, device=x.device)
-    sx = x3.stride(0) if x3.shape[0] > 1 else 0
-    sr = 0
-    if residual is not None:
-        r3 = residual if residual.dim() == 3 else residual.unsqueeze(0)
-        assert r3.dtype == torch.float32 and r3.stride(2) == 1 and r3.stride(1) == cols
-        sr = r3.stride(0) if r3.shape[0] > 1 else 0
-    sg = gamma.stride(0) if gamma.dim() == 2 else 0
+    x3, nb, rows, cols, lead, sx, sr, sg = _ln_views(x, gamma, residual, (torch.float32,))
+    ys = torch.empty(lead + (cols,), dtype=torch.float32, device=x.device) if want_stream else None
+    sp = torch.empty(lead + (4 * cols,), dtype=torch.uint8, device=x.device)
     code = _lib.load().cir_layernorm_split8(x3.data_ptr(), sx, _ptr(residual), sr, gamma.data_ptr(), beta.data_ptr(), sg, _ptr(ys), rows * cols,
                                             sp.data_ptr(), 4 * cols, rows * 4 * cols, rows, cols, nb, float(eps), _stream())
     _lib.check(code, "cir_layernorm_split8")
@@ -408,16 +401,14 @@ def attention_split8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: f
     if mask is not None:
         assert mask.dtype == torch.float32 and mask.shape == (b1, b0, lk) and mask.stride(2) == 1
         ms1, ms0 = mask.stride(0), mask.stride(1)
-    if PROFILE_ATTN is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev = _events() if PROFILE_ATTN is not None else None
     code = _lib.load().cir_attention_split8(
         q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
         v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), _ptr(mask), ms1, ms0,
         out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), b1, b0, d // 64, lq, lk, float(scale), _stream())
-    if PROFILE_ATTN is not None:
-        ev1.record()
-        PROFILE_ATTN.append((4.0 * b1 * b0 * lq * lk * d, ev0, ev1, (lq, lk)))
+    if ev is not None:
+        ev[1].record()
+        PROFILE_ATTN.append((4.0 * b1 * b0 * lq * lk * d, *ev, (lq, lk)))
     _lib.check(code, "cir_attention_split8")
     return Split8Operand(out, d)
 
@@ -441,16 +432,14 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     if mask is not None:
         assert mask.dtype == torch.float32 and mask.shape == (b1, b0, lk) and mask.stride(2) == 1
         ms1, ms0 = mask.stride(0), mask.stride(1)
-    if PROFILE_ATTN is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev = _events() if PROFILE_ATTN is not None else None
     code = _lib.load().cir_attention(
         q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
         v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), _ptr(mask), ms1, ms0, _ptr(kv_index),
         out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), b1, b0, d // 64, lq, lk, float(scale), _DT[q.dtype], _stream())
-    if PROFILE_ATTN is not None:
-        ev1.record()
-        PROFILE_ATTN.append((4.0 * b1 * b0 * lq * lk * d, ev0, ev1, (lq, lk)))
+    if ev is not None:
+        ev[1].record()
+        PROFILE_ATTN.append((4.0 * b1 * b0 * lq * lk * d, *ev, (lq, lk)))
     _lib.check(code, "cir_attention")
     return out
 
@@ -506,16 +495,14 @@ def cross_attention_folded(q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, 
     if mask is not None:       # additive fp32 key mask (T, N), shared by the two branches
         _need_cuda(mask)
         assert mask.dtype == torch.float32 and mask.shape == (t_n, n) and mask.stride(1) == 1
-    if PROFILE_ATTN is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    ev = _events() if PROFILE_ATTN is not None else None
     code = _lib.load().cir_cross_attention_folded(q.data_ptr(), q.stride(0), q.stride(1), x.data_ptr(), x.stride(0), wkt.data_ptr(), wvp.data_ptr(), d * d,
                                                   bv.data_ptr(), _ptr(mask), mask.stride(0) if mask is not None else 0,
                                                   out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), t_n, l, n, d, heads,
                                                   float(scale), _DT[x.dtype], _stream())
-    if PROFILE_ATTN is not None:
-        ev1.record()      # executed flops: per (candidate, branch) 2 x (H L x 64 x D) projections + 2 x (H L x D x N) products
-        PROFILE_ATTN.append((2.0 * t_n * 2 * (2 * heads * l * 64 * d + 2 * heads * l * d * n), ev0, ev1, ("folded", l, n)))
+    if ev is not None:
+        ev[1].record()    # executed flops: per (candidate, branch) 2 x (H L x 64 x D) projections + 2 x (H L x D x N) products
+        PROFILE_ATTN.append((2.0 * t_n * 2 * (2 * heads * l * 64 * d + 2 * heads * l * d * n), *ev, ("folded", l, n)))
     _lib.check(code, "cir_cross_attention_folded")
     return out
 

@@ -17,8 +17,8 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.bfloat16, torch.float16]
-CANARY = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FC1, torch.float16: 0x7E01, torch.int64: 0x7EADBEEF7EADBEEF}   # NaN patterns
-_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.int64: torch.int64}
+CANARY = {torch.float32: 0x7FC0DEAD, torch.bfloat16: 0x7FC1, torch.float16: 0x7E01, torch.int64: 0x7EADBEEF7EADBEEF, torch.uint8: 0xA5}   # NaN patterns (uint8: split8 rows)
+_INT = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.int64: torch.int64, torch.uint8: torch.uint8}
 
 
 @pytest.fixture(scope="module")
@@ -371,3 +371,63 @@ def test_folded_cross_attention_guard_bands(ops, dtype, t_n, l, n):
     o2 = torch.empty((t_n, l, 2, D), dtype=dtype, device="cuda")
     ops.attention(q.view(2, t_n, l, D).permute(1, 0, 2, 3), kv[:, :, 0::2].permute(0, 2, 1, 3), kv[:, :, 1::2].permute(0, 2, 1, 3), o2.permute(0, 2, 1, 3), 0.125)
     assert (out.float() - o2.float()).abs().max().item() < (6.5e-2 if dtype == torch.bfloat16 else 4e-3)     # (two roundings: up to two bf16 ulps of 2^-5 at |ctx| ~ 4)
+
+
+# ------------------------------------------------------------------------------------------------ the 128 x 128 shell
+def _rnd(shape, dtype, seed, scale=1.0):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return (torch.randn(shape, generator=g) * scale).to(dtype).cuda()
+
+
+@pytest.mark.parametrize("case", ["f32", "f32-res", "f32-gelu", "f32-gelu-res", "f16-out0", "f16-out0-res32", "f16-out1-res32", "f16-out2-res16",
+                                  "split8-res", "split8-rows-gelu"])
+def test_gemm128_outputs_do_not_depend_on_their_tile(ops, case):
+    """Output element (m, n) of the 128 x 128 kernels depends on A row m, W row n, bias n and residual (m, n) alone: a ragged problem computed
+    directly has the bits of the top-left corner of a tile-aligned problem whose padding rows of A and W, bias tail and residual tail hold
+    other random data.  Pins what the kernels share - edge clamps, predicated stores, the W-row permutation - for the instantiations that
+    have no 256 x 256 partner to be compared with, at two m-tiles and a ragged n-tile; every ragged output sits inside canaries."""
+    from candidate_reranking_cir_amd import lib
+    m, mb, nbig = 130, 256, 256
+    res_kind = "32" if case.endswith(("-res", "-res32")) else "16" if case.endswith("-res16") else None
+    act = 1 if "gelu" in case else 0
+    lib.set_tuning(lib.TUNE_GEMM_TILE, 128)
+    try:
+        if case.startswith("split8"):
+            rows_out = case == "split8-rows-gelu"
+            n, k = (192 if rows_out else 144), 256
+            a8 = ops.split8(_rnd((mb, k), torch.float32, 1))
+            wrows, e1, e2 = ops.split_weight8(_rnd((nbig, k), torch.float32, 2, 0.1).cpu())._split8     # ONE pack: per-tensor exponents shared by both problems
+            wrows = wrows.cuda()
+            bias = _rnd((nbig,), torch.float32, 3)
+            res = _rnd((mb, nbig), torch.float32, 4) if res_kind else None
+            big = ops._gemm_split8(a8, (wrows, e1, e2), bias, res, act, None)
+            if not rows_out:
+                guard = Guarded(m, n, torch.float32)
+                ops._gemm_split8(ops.Split8Operand(a8.rows[:m], k), (wrows[:n], e1, e2), bias[:n], res[:m, :n] if res_kind else None, act, guard.view)
+                torch.cuda.synchronize()
+                guard.assert_intact(case)
+                assert torch.equal(guard.view, big[:m, :n])
+            else:       # ops allocates split8 rows itself: the C entry point, into a guarded view
+                guard = Guarded(m, 4 * n, torch.uint8)
+                o = guard.view
+                lib.check(lib.load().cir_gemm_split8(a8.rows.data_ptr(), a8.rows.stride(0), 0, wrows.data_ptr(), wrows.stride(0), 0, bias.data_ptr(), 0,
+                                                     None, 0, 0, o.data_ptr(), o.stride(0), 0, m, n, k, 1, act, 1, e1, e2,
+                                                     torch.cuda.current_stream().cuda_stream), "cir_gemm_split8")
+                torch.cuda.synchronize()
+                guard.assert_intact(case)
+                for lo, hi, width in ((0, 2, 2), (2, 3, 1), (3, 4, 1)):          # [N fp16 | N e4m3 | N e4m3]: each part's first n features
+                    assert torch.equal(o[:, lo * n:hi * n], big.rows[:m, lo * nbig:lo * nbig + width * n]), (case, lo)
+        else:
+            dt = torch.float32 if case.startswith("f32") else torch.float16
+            n, k = 144, (96 if dt == torch.float32 else 128)
+            out_dt = torch.float32 if (dt == torch.float32 or "out1" in case) else torch.float16
+            a, w, bias = _rnd((mb, k), dt, 1), _rnd((nbig, k), dt, 2, 0.1), _rnd((nbig,), torch.float32, 3)
+            res = _rnd((mb, nbig), torch.float32 if res_kind == "32" else torch.float16, 4) if res_kind else None
+            big = ops.gemm(a, w, bias, residual=res, act=act, out_dtype=out_dt)
+            guard = Guarded(m, n, out_dt)
+            ops.gemm(a[:m], w[:n], bias[:n], residual=res[:m, :n] if res_kind else None, act=act, out_dtype=out_dt, out=guard.view)
+            torch.cuda.synchronize()
+            guard.assert_intact(case)
+            assert torch.equal(guard.view, big[:m, :n])
+    finally:
+        lib.set_tuning(lib.TUNE_GEMM_TILE, 0)

@@ -1,5 +1,6 @@
 """Host-side logic that needs no GPU: metric code against the reference's own metric arithmetic
 (tests/golden/metrics.npz), caption joining, tokenizer double, state-dict layout, config loader."""
+import itertools
 import json
 import os
 
@@ -122,3 +123,149 @@ def test_layernorm_fold_and_operand_split_packings():
     assert cat.shape == (2 * n, 3 * k) and cat.dtype == torch.float16 and torch.equal(cat[:, :k], cat[:, k:2 * k])
     rec = cat[:, :k].double() + cat[:, 2 * k:].double()
     assert ((rec - w32.double()).abs() <= w32.double().abs() * 2.0 ** -21 + 2.0 ** -25).all()
+
+
+# ---- ops.gemm_kernel_name: the one statement of the GEMM family's dispatch rule that bench.py's roofline block and tools/pmc_summary.py rely on.
+# Expected names RECORDED from the function as it stood before the family shared one rule (one letter per grid row, itertools.product order).
+_KN_M, _KN_N, _KN_K, _KN_B = (64, 2048, 49000), (128, 256, 768, 3072), (64, 192, 768), (1, 2)
+_KN_T = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
+_KN_NAMES = ['cir::gemm_kernel<__bf16,0>', 'cir::gemm_kernel<_Float16,0>', 'cir::gemm_kernel<float,1>', 'cir::gemm_kernel<__bf16,1>', 'cir::gemm_kernel<_Float16,1>', 'cir::gemm_kernel<__bf16,2>', 'cir::gemm_kernel<_Float16,2>', 'cir::gemm256_kernel<__bf16,false,false,float,0>', 'cir::gemm256_kernel<_Float16,false,false,float,0>', 'cir::gemm256_kernel<__bf16,true,false>', 'cir::gemm256_kernel<_Float16,true,false>', 'cir::gemm256_kernel<__bf16,false,false,_Float16,0>', 'cir::gemm256_kernel<__bf16,false,false,float,1>', 'cir::gemm256_kernel<_Float16,false,false,float,1>', 'cir::gemm256_kernel<__bf16,false,false,_Float16>', 'cir::gemm256_kernel<__bf16,false,false>', 'cir::gemm256_kernel<_Float16,false,false>', 'cir::gemm256_kernel<__bf16,true,true>', 'cir::gemm256_kernel<_Float16,true,true>', 'cir::gemm256_kernel<_Float16,false,true,_Float16,0>', 'cir::gemm256_kernel<__bf16,false,true,_Float16,0>']
+_KN_ROWS = (
+    "aaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggf"
+    "ffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcc"
+    "caaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbq"
+    "cccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccddde"
+    "eecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccff"
+    "fbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggccc"
+    "aaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggf"
+    "ffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbgggfffgggcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcc"
+    "caaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbb"
+    "cccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccddde"
+    "eecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccff"
+    "fbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggccc"
+    "aahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggf"
+    "ffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbggtffuggtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcc"
+    "caaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbb"
+    "cccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddje"
+    "ekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccff"
+    "lbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggccc"
+    "aaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggf"
+    "ffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcc"
+    "caaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbq"
+    "cccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccddde"
+    "eecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccff"
+    "fbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggccc"
+    "aaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggf"
+    "ffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbgggfffgggcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcc"
+    "caaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbb"
+    "cccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccddde"
+    "eecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccff"
+    "fbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggccc"
+    "aahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggf"
+    "ffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbggtffuggtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcc"
+    "caaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbb"
+    "cccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddje"
+    "ekcccffobbncccaapbbqcccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggccchahibicccjdjkekccclf"
+    "libicccmamnbncccjdjkekcccofonbncccpapqbqcccjdjkekcccofoqbqcccaaabbbcccrdrsescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbtgtufutgtcccgggfffgggcccgggfffgggccc"
+    "aaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggf"
+    "ffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbqcccddjeekcccffobbqcc"
+    "caaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaahbbicccddjeekcccfflbbicccaambbncccddjeekcccffobbncccaapbbq"
+    "cccddjeekcccffobbqcccaaabbbcccddreescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbggtffuggtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccddde"
+    "eecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccff"
+    "fbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggccc"
+    "aaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggf"
+    "ffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbgggfffgggcccgggfffgggcccgggfffgggccchahibicccjdjkekccclflibicccmamnbncccjdjkekcccofonbncccpapqbqcccjdjkekcccofoqbqcccaaabbbcccrdrsescccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbtgtufutgtcccgggfffgggcccgggfffgggccchahibicccjdjkekccclflibicccmamnbncccjdjkekcccofonbncccpapqbqcccjdjkekcccofoqbqcccaaabbbcccrdrsescccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbtgtufutgtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcc"
+    "caaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbb"
+    "cccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccddde"
+    "eecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccff"
+    "fbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggccc"
+    "hahibicccjdjkekccclflibicccmamnbncccjdjkekcccofonbncccpapqbqcccjdjkekcccofoqbqcccaaabbbcccrdrsescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbtgtufutgtcccgggf"
+    "ffgggcccgggfffgggccchahibicccjdjkekccclflibicccmamnbncccjdjkekcccofonbncccpapqbqcccjdjkekcccofoqbqcccaaabbbcccrdrsescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecc"
+    "cbbbtgtufutgtcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeeccc"
+    "bbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccb"
+    "bbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcc"
+    "caaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggcccaaabbbcccdddeeecccfffbbbcccaaabbbcccdddeeecccfffbbbcccaaabbb"
+    "cccdddeeecccfffbbbcccaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbgggfffgggcccgggfffgggcccgggfffgggccchahibicccjdjkekccclflibicccmamnbncccjdjk"
+    "ekcccofonbncccpapqbqcccjdjkekcccofoqbqcccaaabbbcccrdrsescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbtgtufutgtcccgggfffgggcccgggfffgggccchahibicccjdjkekccclf"
+    "libicccmamnbncccjdjkekcccofonbncccpapqbqcccjdjkekcccofoqbqcccaaabbbcccrdrsescccbbbaaabbbcccdddeeecccbbbaaabbbcccdddeeecccbbbtgtufutgtcccgggfffgggcccgggfffgggccc")
+_KN_S8NAMES = ['cir::gemm256_kernel<split8,residual>', 'cir::gemm256_kernel<split8,split8-out>', 'cir::gemm256_kernel<split8>', 'cir::gemm_split8_kernel']
+_KN_S8ROWS = 'ddddddddddddddddddddddddddddddddddddddddddddddddddddddddddddcabcddddddddcabccabccabccabccabccabc'
+
+
+def test_gemm_kernel_name_reproduces_the_recorded_dispatch():
+    from candidate_reranking_cir_amd import ops
+    rows = iter(_KN_ROWS)
+    n_rows = 0
+    for m, n, k, nb, r, act, o, op, tile in itertools.product(_KN_M, _KN_N, _KN_K, _KN_B, (None, "f32", "f16"), (0, 1, 2), ("operand", "f32", "f16"),
+                                                              ("bf16", "f16", "f32"), (0, 128, 256)):
+        in_dt = _KN_T[op]
+        out_dt = in_dt if o == "operand" else _KN_T[o]
+        res_dt = None if r is None else _KN_T[r]
+        # the combinations ops.gemm asserts against: an fp16 residual without an fp16 out; an fp16 out from non-fp16 operands with an fp32 residual
+        if res_dt == torch.float16 and out_dt != torch.float16:
+            continue
+        if res_dt == torch.float32 and out_dt == torch.float16 and in_dt != torch.float16:
+            continue
+        want = _KN_NAMES[ord(next(rows)) - 97]
+        assert ops.gemm_kernel_name(m, n, k, nb, r is not None, act, out_dt, in_dt, tile=tile, res_dtype=res_dt) == want, (m, n, k, nb, r, act, o, op, tile)
+        n_rows += 1
+    assert n_rows == len(_KN_ROWS) == 12960
+    # every kernel name of the two recorded per-shape profiles (bf16 operands; the residual is fp16 with an fp16 out, else fp32)
+    n_prof = 0
+    for rnd in ("r5", "r6"):
+        with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", f"{rnd}_secondary", "gemm_shapes.json")) as f:
+            for s in json.load(f)["shapes"]:
+                out_dt = getattr(torch, s["out"])
+                res_dt = (torch.float16 if out_dt == torch.float16 else torch.float32) if s["residual"] else None
+                assert ops.gemm_kernel_name(s["M"], s["N"], s["K"], s["batch"], s["residual"], s["act"], out_dt, torch.bfloat16, res_dtype=res_dt) == s["kernel"], s
+                n_prof += 1
+    assert n_prof == 52
+    # the LayerNorm-folded GEMM: the name gemm_ln recorded, whatever the shape
+    for act in (0, 1):
+        assert ops.gemm_kernel_name(50000, 3072, 768, 1, False, act, torch.float16, torch.float16, form="ln") == f"cir::gemm256_kernel<_Float16,false,false,float,{act},true>"
+    # split8 operands, for what _gemm_split8 passes (GELU = split8 rows out, no residual): the rule it carried inline, which knew neither the
+    # leading-dimension bound nor the tile override ...
+    rows = iter(_KN_S8ROWS)
+
+    def s8(m, n, nb, act, res, **kw):
+        return ops.gemm_kernel_name(m, n, 768, nb, res, act, torch.uint8 if act == 1 else torch.float32, torch.float32, form="split8", **kw)
+    for m, n, nb, (act, res) in itertools.product(_KN_M, _KN_N, _KN_B, ((0, False), (0, True), (1, False), (2, False))):
+        assert s8(m, n, nb, act, res) == _KN_S8NAMES[ord(next(rows)) - 97], (m, n, nb, act, res)
+    assert next(rows, None) is None
+    # ... and THESE rows differ from that inline rule on purpose - they follow the library (csrc/gemm.hip: gemm_tile): a leading dimension
+    # of 2^21 or more keeps the 128 x 128 kernel (the inline rule said 256), and so does a forced 128; a forced 256 takes a problem the
+    # automatic rule leaves to the 128 kernel (the inline rule said 128) unless a leading dimension is out of the 256 kernel's range
+    assert s8(49000, 768, 1, 0, False) == "cir::gemm256_kernel<split8>"
+    assert s8(49000, 768, 1, 0, False, lda=1 << 21) == s8(49000, 768, 1, 0, False, ldw=1 << 21) == "cir::gemm_split8_kernel"
+    assert s8(49000, 768, 1, 0, False, lda=(1 << 21) - 8, ldw=(1 << 21) - 8) == "cir::gemm256_kernel<split8>"
+    assert s8(49000, 768, 1, 0, True, tile=128) == "cir::gemm_split8_kernel"
+    assert s8(64, 128, 1, 0, True) == "cir::gemm_split8_kernel" and s8(64, 128, 1, 0, True, tile=256) == "cir::gemm256_kernel<split8,residual>"
+    assert s8(64, 128, 1, 1, False, tile=256) == "cir::gemm256_kernel<split8,split8-out>"
+    assert s8(64, 128, 1, 0, False, tile=256, lda=1 << 21) == "cir::gemm_split8_kernel"
+    # the 16-bit path has the same bound (the mirror this function replaces had none): the library falls back to the 128 x 128 kernel
+    assert ops.gemm_kernel_name(49000, 768, 768, 1, False, 0, torch.float16, torch.bfloat16, lda=1 << 21) == "cir::gemm_kernel<__bf16,2>"
+    assert ops.gemm_kernel_name(49000, 768, 768, 1, False, 0, torch.float16, torch.bfloat16, tile=256, ldw=1 << 21) == "cir::gemm_kernel<__bf16,2>"
