@@ -289,6 +289,15 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
 namespace cir {
 // kernel-selection overrides (cir_set_tuning; misc.hip owns the storage): 0 = automatic
 extern int g_tune[3];
+
+// The finishing pass of the fixed-order sums (train_det.hip): destination j (nout <= 4) receives, ADDED to what it holds, the sums over all
+// `rows` rows of the source columns [src[j] * seg, (src[j] + 1) * seg) of x (row stride ld) - the order is the one cir_colsum_ordered
+// documents.  The `_ordered` entry points of train.hip / train_fused.hip store one row of per-workgroup partial sums per workgroup and
+// finish with this.
+constexpr int kOrdRows = 256;             // rows per first-level block of a long ordered column sum
+constexpr int kEmbChunk = 512;            // rows per chunk of the ordered embedding backward
+struct OrderedDst { float* out[4]; int src[4]; int nout; };
+int colsum_ordered_launch(const float* x, int64_t ld, int64_t rows, int seg, const OrderedDst& d, hipStream_t s);
 }  // namespace cir
 #define CIR_CHECK_PTR(p) do { if ((p) == nullptr) return CIR_EINVAL; } while (0)
 #define CIR_LAUNCH_RESULT() do { hipError_t e_ = hipGetLastError(); return e_ == hipSuccess ? CIR_OK : (int)e_; } while (0)

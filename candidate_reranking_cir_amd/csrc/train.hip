@@ -434,9 +434,11 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const T* P, int64_t ld
 // ---- LayerNorm backward: y = (x - mean) * rstd * gamma + beta over `cols`; x fp32 (the saved pre-LN sum) -----------------
 // dx fp32 (written), dgamma / dbeta fp32 (atomically accumulated: zero them first).  One wave per row, 32 rows per block: the
 // per-column sums of those rows are kept in registers (cols <= 64 * kLnCols) and added once per block, not once per row.
+// ORD (deterministic mode, cir_layernorm_bwd_ordered): the block stores its sums to row blockIdx.x of `part` (2 * cols: dgamma | dbeta) instead.
 constexpr int kLnCols = 16;      // columns per lane: cols <= 1024
+template <bool ORD>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta,
-                                                            int64_t rows, int cols, float eps) {
+                                                            int64_t rows, int cols, float eps, float* part) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float pg[kLnCols], pb[kLnCols];
 #pragma unroll
@@ -486,8 +488,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* x, cons
     for (int i = 0; i < kLnCols; ++i) { red[0][wave][lane + i * 64] = pg[i]; red[1][wave][lane + i * 64] = pb[i]; }
     __syncthreads();
     for (int c = threadIdx.x; c < cols; c += 256) {
-        atomicAdd(dgamma + c, red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
-        atomicAdd(dbeta + c, red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+        if constexpr (ORD) {
+            float* pr = part + (int64_t)blockIdx.x * 2 * cols;
+            pr[c] = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
+            pr[cols + c] = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
+        } else {
+            atomicAdd(dgamma + c, red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
+            atomicAdd(dbeta + c, red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+        }
     }
 }
 
@@ -930,8 +938,24 @@ extern "C" int cir_layernorm_bwd(const float* x, const float* gamma, const float
     if (rows <= 0 || cols <= 0) return CIR_EINVAL;
     if (cols > 64 * kLnCols) return CIR_ESHAPE;
     dim3 grid((unsigned)((rows + 31) / 32)), block(256);
-    hipLaunchKernelGGL(layernorm_bwd_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), x, gamma, dy, dx, dgamma, dbeta, rows, cols, eps);
+    hipLaunchKernelGGL(layernorm_bwd_kernel<false>, grid, block, 0, reinterpret_cast<hipStream_t>(stream), x, gamma, dy, dx, dgamma, dbeta, rows, cols, eps,
+                       (float*)nullptr);
     CIR_LAUNCH_RESULT();
+}
+
+extern "C" int cir_layernorm_bwd_ordered(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int64_t rows,
+                                         int cols, float eps, float* partials, int64_t partial_elems, void* stream) {
+    CIR_CHECK_PTR(x); CIR_CHECK_PTR(gamma); CIR_CHECK_PTR(dy); CIR_CHECK_PTR(dx); CIR_CHECK_PTR(dgamma); CIR_CHECK_PTR(dbeta); CIR_CHECK_PTR(partials);
+    if (rows <= 0 || cols <= 0) return CIR_EINVAL;
+    const int64_t blocks = (rows + 31) / 32;
+    if (cols > 64 * kLnCols || partial_elems < blocks * 2 * cols) return CIR_ESHAPE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(layernorm_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, x, gamma, dy, dx, dgamma, dbeta, rows, cols, eps, partials);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    OrderedDst d{};
+    d.out[0] = dgamma; d.out[1] = dbeta; d.src[1] = 1; d.nout = 2;
+    return colsum_ordered_launch(partials, 2 * (int64_t)cols, blocks, cols, d, s);
 }
 
 extern "C" int cir_eltwise(const void* z, int z_dtype, const float* dy, void* out, int out_dtype, int64_t n, int mode, float p_drop, uint64_t seed,

@@ -87,10 +87,12 @@ __global__ __launch_bounds__(256) void res_ln_train_kernel(const float* t0, cons
 // One wave per row; the per-column sums (dgamma, dbeta, bias gradient) of a block's rows stay in registers and are added once per block.
 // Rows per block trade those atomics against occupancy: at 8192 rows, 32 rows per block are 256 blocks = ONE wave per SIMD, each walking
 // its rows serially through two wave reductions; fewer rows per block were measured and lose (see the launch).
-template <typename T, int ITERS>      // 4 * ITERS rows per block (one wave per row at a time)
+// ORD (deterministic mode, cir_layernorm_bwd_fused_ordered): the block stores its sums to row blockIdx.x of `part` (dgamma | dbeta | bias
+// gradient, `cols` each; the third only when a bias gradient is wanted) instead of adding them.
+template <typename T, int ITERS, bool ORD>      // 4 * ITERS rows per block (one wave per row at a time)
 __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta,
                                                            const float* t_add, T* dt16, float* db1, float* db2, int64_t rows, int cols, float eps,
-                                                           float alpha, float p_drop, uint64_t seed) {
+                                                           float alpha, float p_drop, uint64_t seed, float* part) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
     const uint32_t thr = drop_threshold(p_drop);
@@ -184,6 +186,7 @@ __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const float* x, const
         __syncthreads();
         for (int c = threadIdx.x; c < cols; c += 256) {
             const float v = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
+            if constexpr (ORD) { part[((int64_t)blockIdx.x * (bias ? 3 : 2) + pass) * cols + c] = v; continue; }
             if (pass == 0) atomicAdd(dgamma + c, v);
             else if (pass == 1) atomicAdd(dbeta + c, v);
             else { atomicAdd(db1 + c, v); if (db2 != nullptr) atomicAdd(db2 + c, v); }
@@ -198,7 +201,8 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
     return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
 
-template <typename T, int MODE>      // MODE 0: sums of a;  1: out = a * gelu'(z), sums of out
+// ORD (deterministic mode, cir_rows16_colsum_ordered): `sums` is the partial workspace, the block stores to its row blockIdx.y.
+template <typename T, int MODE, bool ORD>      // MODE 0: sums of a;  1: out = a * gelu'(z), sums of out
 __global__ __launch_bounds__(256) void rows16_colsum_kernel(const T* a, int64_t lda, const T* z, int64_t ldz, T* out, int64_t ldo, float* sums,
                                                             int64_t rows, int cols) {
     typedef typename Elem<T>::x8 X8;
@@ -240,7 +244,8 @@ __global__ __launch_bounds__(256) void rows16_colsum_kernel(const T* a, int64_t 
         float v = 0.f;
 #pragma unroll
         for (int j = 0; j < 8; ++j) v += red[j][threadIdx.x];
-        atomicAdd(sums + cc, v);
+        if constexpr (ORD) sums[(int64_t)blockIdx.y * cols + cc] = v;
+        else atomicAdd(sums + cc, v);
     }
 }
 
@@ -302,9 +307,9 @@ extern "C" int cir_residual_layernorm_train(const float* t0, const float* t1, co
     CIR_LAUNCH_RESULT();
 }
 
-extern "C" int cir_layernorm_bwd_fused(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, const float* t_add,
-                                       void* dt16, float* dbias, float* dbias2, int64_t rows, int cols, float eps, float alpha, float p_drop,
-                                       uint64_t seed, int dtype16, void* stream) {
+// validation shared by cir_layernorm_bwd_fused and its ordered form
+static int ln_bwd_fused_check(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, const float* t_add,
+                              void* dt16, int64_t rows, int cols, float p_drop, int dtype16) {
     CIR_CHECK_PTR(x); CIR_CHECK_PTR(gamma); CIR_CHECK_PTR(dy); CIR_CHECK_PTR(dgamma); CIR_CHECK_PTR(dbeta);
     if (dx == nullptr && dt16 == nullptr) return CIR_EINVAL;
     if (rows <= 0 || cols <= 0 || p_drop < 0.f || p_drop >= 1.f) return CIR_EINVAL;
@@ -312,22 +317,55 @@ extern "C" int cir_layernorm_bwd_fused(const float* x, const float* gamma, const
     if (dtype16 != CIR_BF16 && dtype16 != CIR_F16) return CIR_EDTYPE;
     if (!cir_aligned16(x) || !cir_aligned16(gamma) || !cir_aligned16(dy) || !cir_aligned16(dx) || !cir_aligned16(t_add) ||
         (reinterpret_cast<uintptr_t>(dt16) & 7u)) return CIR_EALIGN;
+    return CIR_OK;
+}
+
+extern "C" int cir_layernorm_bwd_fused(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, const float* t_add,
+                                       void* dt16, float* dbias, float* dbias2, int64_t rows, int cols, float eps, float alpha, float p_drop,
+                                       uint64_t seed, int dtype16, void* stream) {
+    const int bad = ln_bwd_fused_check(x, gamma, dy, dx, dgamma, dbeta, t_add, dt16, rows, cols, p_drop, dtype16);
+    if (bad != CIR_OK) return bad;
     // 32 rows per block.  Measured (tools, round 4; 8192 x 768, dropout + bias sums on): 32 rows 30.6 us, 16 rows 29.6 us, 8 rows 43.3 us -
     // the column-sum atomics (3 x 768 per block) outweigh the occupancy gained
-    const int iters = 8;
-    dim3 block(256);
+    dim3 block(256), grid((unsigned)((rows + 31) / 32));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define CIR_LNB(TT, IT) hipLaunchKernelGGL((ln_bwd_fused_kernel<TT, IT>), dim3((unsigned)((rows + 4 * IT - 1) / (4 * IT))), block, 0, s, x, gamma, dy, dx, dgamma, \
-                                           dbeta, t_add, reinterpret_cast<TT*>(dt16), dbias, dbias2, rows, cols, eps, alpha, p_drop, seed)
-#define CIR_LNB_T(TT) do { (void)iters; CIR_LNB(TT, 8); } while (0)
-    if (dtype16 == CIR_BF16) CIR_LNB_T(__bf16); else CIR_LNB_T(_Float16);
-#undef CIR_LNB_T
+#define CIR_LNB(TT) hipLaunchKernelGGL((ln_bwd_fused_kernel<TT, 8, false>), grid, block, 0, s, x, gamma, dy, dx, dgamma, dbeta, t_add, \
+                                       reinterpret_cast<TT*>(dt16), dbias, dbias2, rows, cols, eps, alpha, p_drop, seed, (float*)nullptr)
+    if (dtype16 == CIR_BF16) CIR_LNB(__bf16); else CIR_LNB(_Float16);
 #undef CIR_LNB
     CIR_LAUNCH_RESULT();
 }
 
-extern "C" int cir_rows16_colsum(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, float* sums, int64_t rows, int cols,
-                                 int mode, int dtype, void* stream) {
+extern "C" int cir_layernorm_bwd_fused_ordered(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta,
+                                               const float* t_add, void* dt16, float* dbias, float* dbias2, int64_t rows, int cols, float eps,
+                                               float alpha, float p_drop, uint64_t seed, int dtype16, float* partials, int64_t partial_elems,
+                                               void* stream) {
+    const int bad = ln_bwd_fused_check(x, gamma, dy, dx, dgamma, dbeta, t_add, dt16, rows, cols, p_drop, dtype16);
+    if (bad != CIR_OK) return bad;
+    CIR_CHECK_PTR(partials);
+    const bool bias = dt16 != nullptr && dbias != nullptr;                      // (as the kernel: dbias2 counts only beside dbias)
+    const int64_t blocks = (rows + 31) / 32;
+    if (partial_elems < blocks * (bias ? 3 : 2) * cols) return CIR_ESHAPE;
+    dim3 block(256), grid((unsigned)blocks);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define CIR_LNB(TT) hipLaunchKernelGGL((ln_bwd_fused_kernel<TT, 8, true>), grid, block, 0, s, x, gamma, dy, dx, dgamma, dbeta, t_add, \
+                                       reinterpret_cast<TT*>(dt16), dbias, dbias2, rows, cols, eps, alpha, p_drop, seed, partials)
+    if (dtype16 == CIR_BF16) CIR_LNB(__bf16); else CIR_LNB(_Float16);
+#undef CIR_LNB
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    OrderedDst d{};
+    d.out[0] = dgamma; d.out[1] = dbeta; d.src[1] = 1; d.nout = 2;
+    if (bias) {
+        d.out[2] = dbias; d.src[2] = 2; d.nout = 3;
+        if (dbias2 != nullptr) { d.out[3] = dbias2; d.src[3] = 2; d.nout = 4; }
+    }
+    return colsum_ordered_launch(partials, (int64_t)(bias ? 3 : 2) * cols, blocks, cols, d, s);
+}
+
+static int rows16_colsum(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, float* sums, int64_t rows, int cols,
+                         int mode, int dtype, float* partials, int64_t partial_elems, void* stream) {
+    const bool ord = partials != nullptr;
     CIR_CHECK_PTR(a);
     if (rows <= 0 || cols <= 0 || mode < 0 || mode > 1) return CIR_EINVAL;
     if (mode == 0 && sums == nullptr) return CIR_EINVAL;
@@ -337,12 +375,31 @@ extern "C" int cir_rows16_colsum(const void* a, int64_t lda, const void* z, int6
     if (!cir_aligned16(a) || !cir_aligned16(z) || !cir_aligned16(out)) return CIR_EALIGN;
     const int64_t row_blocks = (rows + 63) / 64;
     if (row_blocks > 65535) return CIR_ESHAPE;
+    if (ord && partial_elems < row_blocks * cols) return CIR_ESHAPE;
     dim3 grid((cols + 255) / 256, (unsigned)row_blocks), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define CIR_R16(T, MODE) hipLaunchKernelGGL((rows16_colsum_kernel<T, MODE>), grid, block, 0, s, reinterpret_cast<const T*>(a), lda, \
-                                            reinterpret_cast<const T*>(z), ldz, reinterpret_cast<T*>(out), ldo, sums, rows, cols)
-    if (dtype == CIR_BF16) { if (mode) CIR_R16(__bf16, 1); else CIR_R16(__bf16, 0); }
-    else { if (mode) CIR_R16(_Float16, 1); else CIR_R16(_Float16, 0); }
+#define CIR_R16(T, MODE, ORD, SUMS) hipLaunchKernelGGL((rows16_colsum_kernel<T, MODE, ORD>), grid, block, 0, s, reinterpret_cast<const T*>(a), lda, \
+                                                       reinterpret_cast<const T*>(z), ldz, reinterpret_cast<T*>(out), ldo, SUMS, rows, cols)
+#define CIR_R16_T(T) do { if (ord) { if (mode) CIR_R16(T, 1, true, partials); else CIR_R16(T, 0, true, partials); } \
+                          else { if (mode) CIR_R16(T, 1, false, sums); else CIR_R16(T, 0, false, sums); } } while (0)
+    if (dtype == CIR_BF16) CIR_R16_T(__bf16); else CIR_R16_T(_Float16);
+#undef CIR_R16_T
 #undef CIR_R16
-    CIR_LAUNCH_RESULT();
+    if (!ord) CIR_LAUNCH_RESULT();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    OrderedDst d{};
+    d.out[0] = sums; d.nout = 1;
+    return colsum_ordered_launch(partials, cols, row_blocks, cols, d, s);
+}
+
+extern "C" int cir_rows16_colsum(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, float* sums, int64_t rows, int cols,
+                                 int mode, int dtype, void* stream) {
+    return rows16_colsum(a, lda, z, ldz, out, ldo, sums, rows, cols, mode, dtype, nullptr, 0, stream);
+}
+
+extern "C" int cir_rows16_colsum_ordered(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, float* sums, int64_t rows,
+                                         int cols, int mode, int dtype, float* partials, int64_t partial_elems, void* stream) {
+    CIR_CHECK_PTR(sums); CIR_CHECK_PTR(partials);
+    return rows16_colsum(a, lda, z, ldz, out, ldo, sums, rows, cols, mode, dtype, partials, partial_elems, stream);
 }

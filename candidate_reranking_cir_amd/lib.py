@@ -86,6 +86,14 @@ SIGNATURES = {
     "cir_eltwise": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_uint64, c_void_p]),
     "cir_colsum": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     "cir_embed_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    # fixed-order forms (deterministic training mode)
+    "cir_colsum_ordered": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "cir_layernorm_bwd_ordered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_int64, c_void_p]),
+    "cir_layernorm_bwd_fused_ordered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                c_int, c_float, c_float, c_float, c_uint64, c_int, c_void_p, c_int64, c_void_p]),
+    "cir_rows16_colsum_ordered": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64,
+                                          c_void_p]),
+    "cir_embed_bwd_ordered": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "cir_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p]),
     "cir_grads_check": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "cir_adamw_begin": (c_int, [c_void_p, c_float, c_float, c_void_p]),

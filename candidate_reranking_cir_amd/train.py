@@ -19,7 +19,9 @@ values of a target image are projected once per step and their gradients sum ove
 Precision: 16-bit MFMA operands (activations, weights, and every gradient between two dense layers), fp32 accumulation, fp32 residual
 stream and its gradient, fp32 LayerNorm inputs, fp32 weight gradients.
 Dropout is counter-based (seed per site); with p = 0 the pass has no random state - reproducible up to the order of the fp32 atomic adds in
-the column sums / LayerNorm and embedding adjoints - and is what the reference-gradient fixtures pin.
+the column sums / LayerNorm and embedding adjoints - and is what the reference-gradient fixtures pin.  `set_deterministic(True)` (process-wide,
+off by default, read at the start of every backward of the three passes) replaces those atomics by the fixed-order forms of include/cirrank.h:
+the gradients then repeat bit for bit.
 
 `fusion_train(model, ...)` wraps the pair as ONE `torch.autograd.Function`, so the reference's training step runs unchanged:
 `logits = model.img_txt_fusion(z_t, feats, captions)` in `.train()` mode, `loss = F.cross_entropy(logits, gt)`, `loss.backward()`
@@ -35,6 +37,7 @@ import torch
 from . import ops, train_ops as T
 from .train_core import Trainer, _Lin, _Lin2, _cast, _install_grads, _row_split, loss_scale, train_dtype  # noqa: F401  (re-exported)
 from .train_optim import AdamW, cosine_lr_schedule  # noqa: F401  (re-exported)
+from .train_ops import deterministic, set_deterministic  # noqa: F401  (re-exported: the deterministic training mode)
 
 
 class NlvrTrainer(Trainer):
@@ -224,6 +227,7 @@ class NlvrTrainer(Trainer):
     def backward(self, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
         """dlogits (B, B) fp32 -> {parameter name: fp32 gradient} for every text_encoder.* / cls_head.* parameter."""
         sv, g, dt = self.sv, self.geo, self.dtype
+        det = self.slab.read_mode()                                                 # {} or the fixed-order forms' workspace (deterministic mode)
         dev = dlogits.device
         t_n, l, n, d = sv["t_n"], sv["l"], sv["n"], g.hidden_size
         r = t_n * l
@@ -253,7 +257,7 @@ class NlvrTrainer(Trainer):
             wq: list = []                                                           # this layer's weight-gradient products: ONE launch at its end
             dpre3, do16 = ly["ln3"].bwd_res(s["pre3"], dh, dt, dbias=w2.db, p_drop=ph, seed=self._site(i, 0, 5))
             df16 = w2.bwd16(s["f16"], do16, dx_dtype=dt, queue=wq)
-            dz16 = T.gelu_bwd16(df16, s["z16"], sums=w1.db)
+            dz16 = T.gelu_bwd16(df16, s["z16"], sums=w1.db, **det)
             dx = w1.bwd16(s["x16"], dz16, residual=dpre3, queue=wq)                 # (2R, D) fp32: FFN branch + skip
             # the two LayerNorms over m + a_b: d m = dropout'(d pre2_0 + d pre2_1) comes out of the second one's kernel
             merge = ly["merge"]
@@ -298,11 +302,11 @@ class NlvrTrainer(Trainer):
                            *(self._heads(dqkv16.view(2 * r, 3 * d), 2 * t_n, l, j, 3) for j in range(3)))
             ly["qkv"].wgrad(s["h16"], dqkv16, wq, bias=True)
             dh = ly["qkv"].dgrad(dqkv16, torch.float32, residual=dpre1).view(2 * r, d)      # both branches stacked, as the layer below's FFN saw them
-            T.wgrad_grouped(wq)
+            self._wgrad_grouped(wq)
         # branch 1 entered through BertEmbeddings; branch 0 is z_t (frozen stage I)
         de = dh[r:] if ph <= 0 else T.eltwise(dh[r:], T.MODE_DROPOUT, p_drop=ph, seed=self._site(9000))
         dpre_e = self.ln_e.bwd(sv["pre_e"], de)
-        T.embed_bwd(sv["ids"].view(-1), dpre_e, self.dword, self.dpos, l)
+        T.embed_bwd(sv["ids"].view(-1), dpre_e, self.dword, self.dpos, l, **det)
         # the loss-scaled gradient of the target tokens, unscaled for the ViT's own (separately scaled) reverse pass
         self.dfeats = None if dfeats is None else (dfeats if self.grad_scale == 1.0 else T.eltwise(dfeats, T.MODE_SCALE, p_drop=1.0 / self.grad_scale))
         self.dfeats_scale = None if dfeats is None else self.grad_scale            # train_vit.VitTrainer.backward runs under the same scale

@@ -65,6 +65,23 @@ class _Slab:
         self.flat16 = self.flat16t = self.gflat = self.plan = None
         self.checked = None                                                         # (gradient buffer pointer, its "all finite" device flag)
         self._fresh16 = None                                                        # the `key` flat16 was written for
+        self.work = None                  # deterministic mode: the workspace of the fixed-order operators for the backward in flight (else None)
+        self._workspace = None            # ... kept between steps
+
+    def read_mode(self) -> dict:
+        """Read the process-wide deterministic switch (train_ops.set_deterministic) for the backward that starts now.  Returns the keyword
+        the pass and the layer views hand to the train_ops operators that sum across workgroups: {} - the default, atomic forms - or
+        {"work": the trainer's reusable workspace}, which selects their fixed-order forms."""
+        if T.deterministic():
+            if self._workspace is None:
+                self._workspace = T.Workspace()
+            self.work = self._workspace
+        else:
+            self.work = None
+        return self.det_kw()
+
+    def det_kw(self) -> dict:
+        return {} if self.work is None else {"work": self.work}
 
     def _view(self, flat: torch.Tensor, n: str) -> torch.Tensor:
         p = self.params[n]
@@ -169,8 +186,9 @@ class _Lin:
         m, k = x16.shape
         n = self.w16.shape[0]
         dy16 = _cast(dy, x16.dtype)
+        det = self.slab.det_kw()
         if self.db is not None:
-            T.colsum(dy, self.db)
+            T.colsum(dy, self.db, **det)
         # dW (N, K) = dy^T x on cir_bmm (operands read as stored: trans_a), split over row chunks into partial sums so that the
         # 36-tile products of a 768 x 768 weight fill the chip; the partials are summed into dW by the column-sum kernel
         nb = _row_split(m, n, k)
@@ -178,7 +196,7 @@ class _Lin:
             T.bmm(dy16.unsqueeze(0), x16.unsqueeze(0), True, False, out=self.dw.unsqueeze(0), accumulate=True)
         else:
             part = T.bmm(dy16.view(nb, m // nb, n), x16.view(nb, m // nb, k), True, False, out_dtype=torch.float32)
-            T.colsum(part.view(nb, n * k), self.dw.view(-1))
+            T.colsum(part.view(nb, n * k), self.dw.view(-1), **det)
         if not need_dx:
             return None
         if _gemm_ok(m, k, n):                                                       # dx (M, K) = dy (M, N) . (W^T (K, N))^T
@@ -194,8 +212,9 @@ class _Lin:
         dx = dy . W (+ residual: the fp32 gradient arriving over the skip connection, added in the GEMM epilogue) in `dx_dtype`."""
         m, k = x16.shape
         n = self.w16.shape[0]
+        det = self.slab.det_kw()
         if bias and self.db is not None:
-            T.colsum16(dy16, self.db)
+            T.colsum16(dy16, self.db, **det)
         # dW (N, K) += dy^T x with both operands read as stored, the rows split over workgroups so that the 36-tile product of a
         # 768 x 768 weight fills the chip; every workgroup adds its partial tile straight into dW (atomics: no partial tensor)
         if n % 128 == 0 and k % 128 == 0:
@@ -203,8 +222,12 @@ class _Lin:
             # the layer's other weight gradients - ~940 output tiles fill the chip without splitting any tile's rows over workgroups
             if queue is not None:
                 queue.append((dy16, x16, self.dw))
+            elif det:
+                T.wgrad(dy16, x16, self.dw, splits=1)                               # one workgroup per tile: plain adds
             else:
                 T.wgrad(dy16, x16, self.dw)
+        elif det:                                                                   # unsplit: every dW element has one adder
+            T.bmm(dy16.unsqueeze(0), x16.unsqueeze(0), True, False, out=self.dw.unsqueeze(0), accumulate=True)
         else:
             nb = _row_split(m, n, k)
             T.bmm(dy16.unflatten(0, (nb, m // nb)), x16.unflatten(0, (nb, m // nb)), True, False, out=self.dw.unsqueeze(0).expand(nb, n, k),
@@ -278,7 +301,7 @@ class _LN:
         return ops.layernorm(pre, self.g, self.b, self.eps, want32=True, dtype16=dtype, stream_dtype=torch.float32)
 
     def bwd(self, pre: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
-        return T.layernorm_bwd(pre, self.g, dy, self.dg, self.db, self.eps)
+        return T.layernorm_bwd(pre, self.g, dy, self.dg, self.db, self.eps, **self.slab.det_kw())
 
     def fwd_res(self, t0, t1, res, dtype, alpha=1.0, p_drop=0.0, seed=0, **out):
         """(pre, y32, y16) of LayerNorm(dropout(alpha * (t0 + t1)) + res): one launch (cir_residual_layernorm_train)."""
@@ -286,7 +309,7 @@ class _LN:
 
     def bwd_res(self, pre, dy, dtype, **kw):
         """(d pre fp32, 16-bit gradient of the dense branch behind the dropout) - cir_layernorm_bwd_fused."""
-        return T.layernorm_bwd_fused(pre, self.g, dy, self.dg, self.db, self.eps, dtype, **kw)
+        return T.layernorm_bwd_fused(pre, self.g, dy, self.dg, self.db, self.eps, dtype, **kw, **self.slab.det_kw())
 
 
 def train_dtype(model) -> torch.dtype:
@@ -405,6 +428,13 @@ class Trainer:
     def _bind_grads(self, slab: _Slab):
         """Views of the step's gradient buffer that the pass writes directly (here: the BERT embeddings' of both text passes)."""
         self.dword, self.dpos = slab.grad(self._EMB + "word_embeddings.weight"), slab.grad(self._EMB + "position_embeddings.weight")
+
+    def _wgrad_grouped(self, queue: list):
+        """The layer's queued weight gradients in one launch; deterministic mode: one workgroup per output tile (splits = 1, plain adds)."""
+        if self.slab.work is None:
+            T.wgrad_grouped(queue)
+        else:
+            T.wgrad_grouped(queue, splits=1)
 
     def _heads(self, x: torch.Tensor, groups: int, rows: int, part: int = 0, parts: int = 1) -> torch.Tensor:
         return head_view(x, groups, rows, self._nh, self._hd, part, parts)

@@ -12,6 +12,42 @@ from .ops import _DT, _need_cuda, _ptr, _stream
 
 MODE_GELU, MODE_GELU_BWD, MODE_RELU, MODE_RELU_BWD, MODE_DROPOUT, MODE_ADD, MODE_SCALE = 0, 1, 2, 3, 4, 5, 6
 
+# ---- deterministic training mode ---------------------------------------------------------------------------------------------------------
+# Process-wide, like lib.set_tuning; off by default.  Every training-mode backward reads it once, at its start (train_core.Trainer._det_kw),
+# and then takes the fixed-order forms of include/cirrank.h for every sum the default kernels add with fp32 atomics: same weights, inputs,
+# dropout seed, process and device -> bit-identical gradients.  The operators below take the fixed-order form when they are given a
+# `Workspace` (`work=`), the default form otherwise.
+_DETERMINISTIC = [False]
+
+
+def set_deterministic(enabled: bool) -> None:
+    _DETERMINISTIC[0] = bool(enabled)
+
+
+def deterministic() -> bool:
+    return _DETERMINISTIC[0]
+
+
+class Workspace:
+    """The caller-owned work buffers of the fixed-order operators (fp32 partial sums, the embedding adjoint's int32 index): grown on demand,
+    reused by every call of one trainer - launches on one stream use them one after the other."""
+
+    def __init__(self):
+        self._f = self._i = None
+
+    def f32(self, n: int, device) -> torch.Tensor:
+        if self._f is None or self._f.numel() < n or self._f.device != device:
+            self._f = torch.empty((max(int(n), 1),), dtype=torch.float32, device=device)
+        return self._f
+
+    def i32(self, n: int, device) -> torch.Tensor:
+        if self._i is None or self._i.numel() < n or self._i.device != device:
+            self._i = torch.empty((max(int(n), 1),), dtype=torch.int32, device=device)
+        return self._i
+
+
+ORD_ROWS, EMB_CHUNK = 256, 512          # kOrdRows / kEmbChunk of csrc/common.hpp (workspace sizing)
+
 
 def transpose16(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x (R, C) or (B, R, C) 16-bit with unit last stride -> (…, C, R) contiguous."""
@@ -92,9 +128,10 @@ def wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, splits: int = 0) 
 WGRAD_GROUP_MAX = 16
 
 
-def wgrad_grouped(problems) -> None:
+def wgrad_grouped(problems, splits: int = 0) -> None:
     """[(dy (rows, N), x (rows, K), dw (N, K) fp32), ...]: dw_i += dy_i^T x_i, up to 16 problems per launch (cir_wgrad_grouped) - the
-    weight gradients of one encoder layer fill the chip together without row splits."""
+    weight gradients of one encoder layer fill the chip together without row splits.  splits = 1: one workgroup per output tile, no atomics
+    (the deterministic mode)."""
     lib = _lib.load()
     for g0 in range(0, len(problems), WGRAD_GROUP_MAX):
         grp = problems[g0:g0 + WGRAD_GROUP_MAX]
@@ -106,7 +143,7 @@ def wgrad_grouped(problems) -> None:
             assert x.shape[0] == rows and dy.dtype == x.dtype == grp[0][0].dtype and dy.stride(1) == 1 and x.stride(1) == 1
             assert dw.dtype == torch.float32 and dw.shape == (n, k) and dw.stride(1) == 1
             d.dy, d.ldy, d.x, d.ldx, d.dw, d.ldw, d.rows, d.N, d.K, d.splits = dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), dw.data_ptr(), \
-                dw.stride(0), rows, n, k, 0
+                dw.stride(0), rows, n, k, int(splits)
         _lib.check(lib.cir_wgrad_grouped(ctypes.addressof(arr), len(grp), _DT[grp[0][0].dtype], _stream()), "cir_wgrad_grouped")
 
 
@@ -182,12 +219,18 @@ def attention_train_bwd(q4, k4, v4, mask, out4, dout4, lse, dq4, dk4, dv4, scale
                                                    int(seed) & (2 ** 63 - 1), _DT[q4.dtype], _stream()), "cir_attention_train_bwd")
 
 
-def layernorm_bwd(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, dgamma: torch.Tensor, dbeta: torch.Tensor, eps: float) -> torch.Tensor:
-    """x, dy fp32 (rows, cols) contiguous; dgamma / dbeta fp32 (cols) are ACCUMULATED into -> dx fp32."""
+def layernorm_bwd(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, dgamma: torch.Tensor, dbeta: torch.Tensor, eps: float,
+                  work: Optional[Workspace] = None) -> torch.Tensor:
+    """x, dy fp32 (rows, cols) contiguous; dgamma / dbeta fp32 (cols) are ACCUMULATED into -> dx fp32.  `work`: cir_layernorm_bwd_ordered."""
     _need_cuda(x, gamma, dy, dgamma, dbeta)
     rows, cols = x.shape
     assert x.dtype == dy.dtype == gamma.dtype == dgamma.dtype == dbeta.dtype == torch.float32 and x.is_contiguous() and dy.is_contiguous()
     dx = torch.empty_like(x)
+    if work is not None:
+        part = work.f32((rows + 31) // 32 * 2 * cols, x.device)
+        _lib.check(_lib.load().cir_layernorm_bwd_ordered(x.data_ptr(), gamma.data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                                         rows, cols, float(eps), part.data_ptr(), part.numel(), _stream()), "cir_layernorm_bwd_ordered")
+        return dx
     _lib.check(_lib.load().cir_layernorm_bwd(x.data_ptr(), gamma.data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), rows, cols,
                                              float(eps), _stream()), "cir_layernorm_bwd")
     return dx
@@ -216,7 +259,8 @@ def residual_layernorm_train(t0: torch.Tensor, t1: Optional[torch.Tensor], resid
 def layernorm_bwd_fused(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, dgamma: torch.Tensor, dbeta: torch.Tensor, eps: float,
                         dtype16: torch.dtype, t_add: Optional[torch.Tensor] = None, dbias: Optional[torch.Tensor] = None,
                         dbias2: Optional[torch.Tensor] = None, alpha: float = 1.0, p_drop: float = 0.0, seed: int = 0, want_dx: bool = True,
-                        want_dt: bool = True, dx: Optional[torch.Tensor] = None, dt16: Optional[torch.Tensor] = None):
+                        want_dt: bool = True, dx: Optional[torch.Tensor] = None, dt16: Optional[torch.Tensor] = None,
+                        work: Optional[Workspace] = None):
     """Adjoint of `residual_layernorm_train` (cir_layernorm_bwd_fused): x (the saved pre) / dy fp32 (rows, cols) -> (dx fp32: gradient of pre =
     of the residual; dt16: alpha * dropout'(dx + t_add) in `dtype16`, the dense branch's gradient, its column sums accumulated into dbias /
     dbias2).  dgamma / dbeta are accumulated."""
@@ -229,27 +273,49 @@ def layernorm_bwd_fused(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, 
     if dt16 is None and want_dt:
         dt16 = torch.empty((rows, cols), dtype=dtype16, device=x.device)
     assert dt16 is None or (dt16.dtype == dtype16 and dt16.shape == (rows, cols) and dt16.is_contiguous())
+    if work is not None:                                                            # cir_layernorm_bwd_fused_ordered
+        part = work.f32((rows + 31) // 32 * 3 * cols, x.device)
+        _lib.check(_lib.load().cir_layernorm_bwd_fused_ordered(x.data_ptr(), gamma.data_ptr(), dy.data_ptr(), _ptr(dx), dgamma.data_ptr(), dbeta.data_ptr(),
+                                                               _ptr(t_add), _ptr(dt16), _ptr(dbias), _ptr(dbias2), rows, cols, float(eps), float(alpha),
+                                                               float(p_drop), int(seed) & (2 ** 63 - 1), _DT[dtype16], part.data_ptr(), part.numel(),
+                                                               _stream()), "cir_layernorm_bwd_fused_ordered")
+        return dx, dt16
     _lib.check(_lib.load().cir_layernorm_bwd_fused(x.data_ptr(), gamma.data_ptr(), dy.data_ptr(), _ptr(dx), dgamma.data_ptr(), dbeta.data_ptr(),
                                                    _ptr(t_add), _ptr(dt16), _ptr(dbias), _ptr(dbias2), rows, cols, float(eps), float(alpha),
                                                    float(p_drop), int(seed) & (2 ** 63 - 1), _DT[dtype16], _stream()), "cir_layernorm_bwd_fused")
     return dx, dt16
 
 
-def colsum16(a: torch.Tensor, sums: torch.Tensor) -> torch.Tensor:
-    """sums (cols) fp32 += column sums of the 16-bit rows a (rows, cols) (unit last stride, row stride a multiple of 8)."""
+def _rows16_ordered(a, z, out, sums, mode: int, work: Workspace):
+    part = work.f32((a.shape[0] + 63) // 64 * a.shape[1], a.device)
+    _lib.check(_lib.load().cir_rows16_colsum_ordered(a.data_ptr(), a.stride(0), _ptr(z), 0 if z is None else z.stride(0), _ptr(out),
+                                                     0 if out is None else out.stride(0), sums.data_ptr(), a.shape[0], a.shape[1], mode, _DT[a.dtype],
+                                                     part.data_ptr(), part.numel(), _stream()), "cir_rows16_colsum_ordered")
+
+
+def colsum16(a: torch.Tensor, sums: torch.Tensor, work: Optional[Workspace] = None) -> torch.Tensor:
+    """sums (cols) fp32 += column sums of the 16-bit rows a (rows, cols) (unit last stride, row stride a multiple of 8).  `work`: in the
+    fixed order of cir_rows16_colsum_ordered."""
     _need_cuda(a, sums)
     assert a.dim() == 2 and a.stride(1) == 1 and sums.dtype == torch.float32 and sums.shape == (a.shape[1],) and sums.is_contiguous()
+    if work is not None:
+        _rows16_ordered(a, None, None, sums, 0, work)
+        return sums
     _lib.check(_lib.load().cir_rows16_colsum(a.data_ptr(), a.stride(0), None, 0, None, 0, sums.data_ptr(), a.shape[0], a.shape[1], 0, _DT[a.dtype],
                                              _stream()), "cir_rows16_colsum")
     return sums
 
 
-def gelu_bwd16(df: torch.Tensor, z: torch.Tensor, sums: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dz = df * gelu'(z) on 16-bit (rows, cols) tensors; sums (cols) fp32 += column sums of dz (the dense layer's bias gradient)."""
+def gelu_bwd16(df: torch.Tensor, z: torch.Tensor, sums: Optional[torch.Tensor] = None, work: Optional[Workspace] = None) -> torch.Tensor:
+    """dz = df * gelu'(z) on 16-bit (rows, cols) tensors; sums (cols) fp32 += column sums of dz (the dense layer's bias gradient; `work`: in
+    the fixed order of cir_rows16_colsum_ordered)."""
     _need_cuda(df, z, sums)
     assert df.dim() == 2 and df.shape == z.shape and df.dtype == z.dtype and df.stride(1) == 1 and z.stride(1) == 1
     assert sums is None or (sums.dtype == torch.float32 and sums.shape == (df.shape[1],) and sums.is_contiguous())
     out = torch.empty(df.shape, dtype=df.dtype, device=df.device)
+    if work is not None and sums is not None:
+        _rows16_ordered(df, z, out, sums, 1, work)
+        return out
     _lib.check(_lib.load().cir_rows16_colsum(df.data_ptr(), df.stride(0), z.data_ptr(), z.stride(0), out.data_ptr(), out.stride(0), _ptr(sums), df.shape[0],
                                              df.shape[1], 1, _DT[df.dtype], _stream()), "cir_rows16_colsum")
     return out
@@ -280,18 +346,36 @@ def eltwise(z: torch.Tensor, mode: int, dy: Optional[torch.Tensor] = None, out_d
     return out
 
 
-def colsum(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
-    """out (cols) fp32 += column sums of x fp32 (rows, cols) (unit last stride)."""
+def colsum(x: torch.Tensor, out: torch.Tensor, work: Optional[Workspace] = None) -> torch.Tensor:
+    """out (cols) fp32 += column sums of x fp32 (rows, cols) (unit last stride).  `work`: in the fixed order of cir_colsum_ordered."""
     _need_cuda(x, out)
     assert x.dtype == out.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and out.shape == (x.shape[1],)
+    if work is not None:
+        assert out.is_contiguous()
+        blocks = (x.shape[0] + ORD_ROWS - 1) // ORD_ROWS
+        part = work.f32(blocks * x.shape[1] if blocks > 1 else 0, x.device)
+        _lib.check(_lib.load().cir_colsum_ordered(x.data_ptr(), x.stride(0), out.data_ptr(), x.shape[0], x.shape[1], part.data_ptr(), part.numel(),
+                                                  _stream()), "cir_colsum_ordered")
+        return out
     _lib.check(_lib.load().cir_colsum(x.data_ptr(), x.stride(0), out.data_ptr(), x.shape[0], x.shape[1], _stream()), "cir_colsum")
     return out
 
 
-def embed_bwd(ids: torch.Tensor, dy: torch.Tensor, dword: torch.Tensor, dpos: torch.Tensor, length: int):
-    """ids (rows,) int64, dy fp32 (rows, cols): dword[ids[r]] += dy[r], dpos[r % length] += dy[r]."""
+def embed_bwd(ids: torch.Tensor, dy: torch.Tensor, dword: torch.Tensor, dpos: torch.Tensor, length: int, work: Optional[Workspace] = None):
+    """ids (rows,) int64, dy fp32 (rows, cols): dword[ids[r]] += dy[r], dpos[r % length] += dy[r].  `work`: in the fixed order of
+    cir_embed_bwd_ordered (dword (table rows, cols) contiguous)."""
     _need_cuda(ids, dy, dword, dpos)
     assert ids.dtype == torch.int64 and ids.is_contiguous() and dy.dtype == torch.float32 and dy.is_contiguous()
+    if work is not None:
+        rows, cols = dy.shape
+        length = int(length)
+        assert dword.dim() == 2 and dword.shape[1] == cols and dword.is_contiguous() and dpos.is_contiguous() and dpos.numel() >= length * cols
+        chunks, seq_blocks = (rows + EMB_CHUNK - 1) // EMB_CHUNK, ((rows + length - 1) // length + ORD_ROWS - 1) // ORD_ROWS
+        part = work.f32(max(rows * cols if chunks > 1 else 0, seq_blocks * length * cols if seq_blocks > 1 else 0), dy.device)
+        index = work.i32(chunks * dword.shape[0], dy.device)
+        _lib.check(_lib.load().cir_embed_bwd_ordered(ids.data_ptr(), dy.data_ptr(), dword.data_ptr(), dpos.data_ptr(), rows, length, cols, dword.shape[0],
+                                                     part.data_ptr(), part.numel(), index.data_ptr(), index.numel(), _stream()), "cir_embed_bwd_ordered")
+        return
     _lib.check(_lib.load().cir_embed_bwd(ids.data_ptr(), dy.data_ptr(), dword.data_ptr(), dpos.data_ptr(), dy.shape[0], int(length), dy.shape[1], _stream()),
                "cir_embed_bwd")
 

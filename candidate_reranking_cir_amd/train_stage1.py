@@ -150,6 +150,7 @@ class MedTrainer(Trainer):
     def backward(self, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
         """dlogits (B, Bt) fp32 -> {parameter name: fp32 gradient} for the 319 trained tensors."""
         sv, g, dt, slab = self.sv, self.geo, self.dtype, self.slab
+        det = slab.read_mode()                                                      # {} or the fixed-order forms' workspace (deterministic mode)
         dev = dlogits.device
         q_n, l, n, d, seed = sv["q_n"], sv["l"], sv["n"], g.hidden_size, sv["seed"]
         r = q_n * l
@@ -169,7 +170,7 @@ class MedTrainer(Trainer):
             wq: list = []                                                           # this layer's weight gradients: ONE launch at its end
             dpre3, do16 = ly["ln3"].bwd_res(s["pre3"], dh, dt, dbias=ly["w2"].db, p_drop=ph, seed=site_seed(seed, i, SITE_FFN_OUT))
             df16 = ly["w2"].bwd16(s["f16"], do16, dx_dtype=dt, queue=wq)
-            dz16 = T.gelu_bwd16(df16, s["z16"], sums=ly["w1"].db)
+            dz16 = T.gelu_bwd16(df16, s["z16"], sums=ly["w1"].db, **det)
             dc = ly["w1"].bwd16(s["c16"], dz16, residual=dpre3, queue=wq)          # fp32: FFN branch + skip
             dpre2, dd16 = ly["ln2"].bwd_res(s["pre2"], dc, dt, dbias=ly["co"].db, p_drop=ph, seed=site_seed(seed, i, SITE_CROSS_OUT))
             dcx16 = ly["co"].bwd16(s["cx"], dd16, dx_dtype=dt, queue=wq)
@@ -190,9 +191,9 @@ class MedTrainer(Trainer):
                                   self._heads(dctx16, q_n, l), s["sa"], *(self._heads(dqkv16, q_n, l, j, 3) for j in range(3)), self._scale, pa,
                                   site_seed(seed, i, SITE_SELF_ATTN), out32=self._heads(s["ctx32"], q_n, l))
             dh = ly["qkv"].bwd16(s["h16"], dqkv16, bias=True, residual=dpre1, queue=wq)
-            T.wgrad_grouped(wq)
+            self._wgrad_grouped(wq)
         de = dh if ph <= 0 else T.eltwise(dh, T.MODE_DROPOUT, p_drop=ph, seed=site_seed(seed, 0, SITE_EMB))
-        T.embed_bwd(sv["ids"].view(-1), self.ln_e.bwd(sv["pre_e"], de), self.dword, self.dpos, l)
+        T.embed_bwd(sv["ids"].view(-1), self.ln_e.bwd(sv["pre_e"], de), self.dword, self.dpos, l, **det)
         self.sv = None                                                              # (the saved activations are released with the pass)
         return self._finish_backward()
 

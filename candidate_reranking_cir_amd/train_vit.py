@@ -136,6 +136,7 @@ class VitTrainer(Trainer):
             raise RuntimeError("img_embed (train mode): the parameters were updated (optimizer step) between this forward and its backward - "
                                "the reverse pass would run on other weights than the forward did")
         slab = self.slab
+        det = slab.read_mode()                                                      # {} or the fixed-order forms' workspace (deterministic mode)
         slab.gflat = torch.zeros_like(slab.flat32)
         self._bind_grads(slab)
         d = geo.width
@@ -169,7 +170,7 @@ class VitTrainer(Trainer):
             # x2 = x1 + DropPath(fc2(gelu(fc1(LayerNorm2(x1)))))
             g16 = branch_grad(g, i, 1)
             df16 = blk["fc2"].bwd16(s["f16"], g16, dx_dtype=dt, bias=True, queue=wq)
-            dz16 = T.gelu_bwd16(df16, s["z16"], sums=blk["fc1"].db)
+            dz16 = T.gelu_bwd16(df16, s["z16"], sums=blk["fc1"].db, **det)
             dh2 = blk["fc1"].bwd16(s["h2"], dz16, queue=wq)                         # (B N, D) fp32
             g = T.eltwise(blk["ln2"].bwd_res(s["x1"], dh2, dt, want_dt=False)[0], T.MODE_ADD, g)
             # x1 = x + DropPath(proj(attention(LayerNorm1(x))))
@@ -181,11 +182,11 @@ class VitTrainer(Trainer):
                                   heads(dqkv16, 0), heads(dqkv16, 1), heads(dqkv16, 2), self._scale, 0.0, 0, out32=c4(s["ctx32"]))
             dh = blk["qkv"].bwd16(s["h16"], dqkv16, bias=True, queue=wq)
             g = T.eltwise(blk["ln1"].bwd_res(s["x"], dh, dt, want_dt=False)[0], T.MODE_ADD, g)
-            T.wgrad_grouped(wq)
+            self._wgrad_grouped(wq)
         # x0 = cat(cls, patch_embed(image)) + pos_embed (vit.py:182-187)
         g3 = g.view(bsz, n, d)
-        T.colsum(g.view(bsz, n * d), self.dpos.reshape(-1))
-        T.colsum(g3[:, 0], self.dcls)
+        T.colsum(g.view(bsz, n * d), self.dpos.reshape(-1), **det)
+        T.colsum(g3[:, 0], self.dcls, **det)
         dproj16 = _cast(g3[:, 1:].contiguous().view(bsz * (n - 1), d), dt)
         self.pe.bwd16(sv["patches"], dproj16, need_dx=False, bias=True)             # pixels are inputs
         return self._finish_backward()

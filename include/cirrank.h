@@ -417,6 +417,54 @@ int cir_eltwise(const void* z, int z_dtype, const float* dy, void* out, int out_
 int cir_colsum(const float* x, int64_t ld, float* out, int64_t rows, int cols, void* stream);
 /* BertEmbeddings backward (nlvr_encoder.py:49-91): dword[ids[r]] += dy[r], dpos[r % L] += dy[r] (fp32, atomics). */
 int cir_embed_bwd(const int64_t* ids, const float* dy, float* dword, float* dpos, int64_t rows, int L, int cols, void* stream);
+/* Fixed-order forms (deterministic training mode; train_det.hip and the `_ordered` launches of train.hip / train_fused.hip).  The operators
+ * above that add across workgroups with fp32 atomics (cir_layernorm_bwd, cir_layernorm_bwd_fused, cir_rows16_colsum, cir_colsum,
+ * cir_embed_bwd) have a twin here that computes the same sums in an order fixed by the shapes alone: same inputs, same device, same build ->
+ * the same bits, call after call.  Every destination is still ACCUMULATED (old + sum).  The workspaces are the caller's (`partials`: fp32,
+ * `partial_elems` elements; contents undefined before and after), nothing is allocated or synchronised, a workspace that is too small is
+ * refused with CIR_ESHAPE before any launch.  No workgroup waits for another: partial sums are stored with plain stores and added by a later
+ * launch on the same stream.
+ *
+ * cir_colsum_ordered: out[c] += sum_r x[r][c], ld >= cols.  The order: the rows are cut into blocks of 256.  Inside a block, row lane l
+ * (0 .. 7) adds rows l, l + 8, l + 16, ... in ascending order into one fp32 accumulator that starts at 0, and the eight lanes are combined as
+ * ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).  With one block (rows <= 256) that value is added to out[c].  With B > 1 blocks the B block
+ * sums are stored to partials (needs B * cols elements), summed over the blocks by the same rule (lane l adds block sums l, l + 8, ...; all
+ * B of them form ONE block here, whatever B), and the result is added to out[c].  rows <= 65535 * 256.
+ * "The finishing sum" below is this operator applied to one row of partial sums per workgroup: workgroup sums in ascending workgroup order
+ * per lane, eight lanes, the fixed tree, then added to the destination. */
+int cir_colsum_ordered(const float* x, int64_t ld, float* out, int64_t rows, int cols, float* partials, int64_t partial_elems, void* stream);
+/* cir_layernorm_bwd with dgamma / dbeta in a fixed order: workgroup b (rows 32 b .. 32 b + 31) sums its rows as cir_layernorm_bwd does (wave w
+ * takes rows 32 b + 4 i + w for i = 0 .. 7 in that order; the four waves are added 0 + 1 + 2 + 3 left to right) and stores the 2 * cols sums
+ * to row b of partials; then the finishing sum over the ceil(rows / 32) workgroups.  partial_elems >= ceil(rows / 32) * 2 * cols.  dx is
+ * bit-identical to cir_layernorm_bwd's. */
+int cir_layernorm_bwd_ordered(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int64_t rows, int cols,
+                              float eps, float* partials, int64_t partial_elems, void* stream);
+/* cir_layernorm_bwd_fused likewise: workgroup b (32 rows, wave w rows 32 b + 4 i + w in order, waves combined (0 + 1) + (2 + 3)) stores
+ * dgamma | dbeta | bias-gradient sums (the third only when dt16 and dbias are given) to row b of partials, then the finishing sum; dbias2
+ * receives the same bias sums as dbias.  partial_elems >= ceil(rows / 32) * (3 or 2) * cols.  dx / dt16 are bit-identical to the plain form's. */
+int cir_layernorm_bwd_fused_ordered(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, const float* t_add,
+                                    void* dt16, float* dbias, float* dbias2, int64_t rows, int cols, float eps, float alpha, float p_drop,
+                                    uint64_t seed, int dtype16, float* partials, int64_t partial_elems, void* stream);
+/* cir_rows16_colsum (both modes) likewise; sums is required.  Workgroup b covers rows 64 b .. 64 b + 63: row lane l (0 .. 7) adds rows
+ * 64 b + 8 i + l for i = 0 .. 7 in order, the lanes are added 0 + 1 + ... + 7 left to right, the sums go to row b of partials, then the
+ * finishing sum.  partial_elems >= ceil(rows / 64) * cols.  `out` (mode 1) is bit-identical to the plain form's. */
+int cir_rows16_colsum_ordered(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, float* sums, int64_t rows, int cols,
+                              int mode, int dtype, float* partials, int64_t partial_elems, void* stream);
+/* cir_embed_bwd in a fixed order; ids outside [0, table_rows) are skipped.
+ * dword: the rows are cut into chunks of 512.  Inside a chunk the rows of one id are added in ascending row order, starting from the first
+ * of them.  With one chunk that sum is added to dword[id].  Otherwise the chunk sums of an id are added in ascending chunk order, starting
+ * from the first chunk that holds the id, and the total is added to dword[id] (one plain read-modify-write per element: each id has one
+ * owner).  A heavy id - the padding id fills half of a stage-I batch - is so summed by many workgroups of at most 512 rows each.
+ * dpos[l] += the ordered column sum (cir_colsum_ordered's order) of dy read as (ceil(rows / L), L * cols) - the rows r = l, l + L, l + 2 L, ...
+ * of dy; a short last sequence simply ends the lists of the positions it lacks.
+ * index: int32 workspace, index_elems >= ceil(rows / 512) * table_rows (first row of each id per chunk, by integer atomic min);
+ * partial_elems >= max(rows * cols if rows > 512, S * L * cols if S > 1) with S = ceil(ceil(rows / L) / 256). */
+int cir_embed_bwd_ordered(const int64_t* ids, const float* dy, float* dword, float* dpos, int64_t rows, int L, int cols, int64_t table_rows,
+                          float* partials, int64_t partial_elems, int32_t* index, int64_t index_elems, void* stream);
+/* The weight gradients need no twin: cir_wgrad / cir_wgrad_grouped with splits = 1 give every 128 x 128 tile of dw to ONE workgroup, which
+ * adds its sum over all 64-row steps with a plain read-modify-write; the tail (rows % 64) then runs as ONE cir_bmm batch item (accumulate 2,
+ * nb1 = nb2 = 1) after it on the same stream: every element of dw has exactly one adder there too, so the atomic add is old + value.  cir_bmm
+ * with accumulate 1 and one batch item per C is a single read-modify-write per element as well. */
 /* torch.optim.AdamW step in place on fp32 parameter / moments (stage2_train.py:120-126 builds that optimizer). */
 int cir_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                    int step, void* stream);

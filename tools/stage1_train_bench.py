@@ -1,7 +1,7 @@
 """Timing of the stage-I training step (stage1_train.py:170-192 on BLIP_Retrieval.img_txt_fusion(..., train=True)): forward, cross-entropy,
 backward and train.AdamW.step at the reference's geometry (full med_config, dropout 0.1 / 0.1, 577 image tokens), one JSON line.
 
-    python tools/stage1_train_bench.py [--batch 1024] [--length 32] [--tokens 577] [--dtype f16|bf16] [--steps 10] [--warmup 3]
+    python tools/stage1_train_bench.py [--batch 1024] [--length 32] [--tokens 577] [--dtype f16|bf16] [--steps 10] [--warmup 3] [--deterministic]
 
 ms per step from device events around the timed steps (after the warm-up); algorithmic FLOPs counted from the shapes below (the products
 the reference computes - the attention backward's recomputed scores are not credited), and their share of the dense 16-bit MFMA peak.
@@ -47,7 +47,9 @@ def main():
     ap.add_argument("--dtype", default="f16", choices=("f16", "bf16"))
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--deterministic", action="store_true", help="train.set_deterministic(True): the fixed-order forms of every cross-workgroup sum")
     a = ap.parse_args()
+    train.set_deterministic(a.deterministic)
     b, l, n = a.batch, a.length, a.tokens
     dev = torch.device("cuda")
     g = cfgmod.BertGeometry.from_dict(dict(hidden_size=768, num_attention_heads=12, num_hidden_layers=12, intermediate_size=3072, layer_norm_eps=1e-12,
@@ -84,7 +86,7 @@ def main():
     ms = e0.elapsed_time(e1) / a.steps
     fwd, bwd = step_flops(b, l, n)
     tflops = (fwd + bwd) / (ms * 1e-3) / 1e12
-    print(json.dumps({"workload": "stage1_train_step", "B": b, "L": l, "N": n, "dtype": a.dtype, "steps": a.steps, "warmup": a.warmup,
+    print(json.dumps({"workload": "stage1_train_step", "B": b, "L": l, "N": n, "dtype": a.dtype, "deterministic": train.deterministic(), "steps": a.steps, "warmup": a.warmup,
                       "ms_per_step": round(ms, 3), "tflop_forward": round(fwd / 1e12, 3), "tflop_backward": round(bwd / 1e12, 3),
                       "achieved_tflops": round(tflops, 1), "peak_tflops": PEAK_TFLOPS, "frac_of_peak": round(tflops / PEAK_TFLOPS, 4),
                       "loss": round(float(loss.detach()), 5), "skipped_steps": opt.skipped_steps,
