@@ -118,6 +118,8 @@ class _EngineHost(nn.Module):
                                                # 0 / False = the f32-input MFMA
         self.text_stream32_from = None         # two-branch encoder: layers >= this index keep their residual stream in fp32 (None: `stream_dtype`
                                                # everywhere) - `set_text_stream32_from`
+        self.long_caption_fold = False         # two-branch encoder: captions of 33-64 tokens take the long-caption query-side fold instead of the
+                                               # projected K|V path (`set_long_caption_fold`; off by default)
         self.graph_candidates = 0              # `score` calls with at most this many candidate rows replay a captured HIP graph per
                                                # shape (0 = off; `enable_graphs`): single-query serving is launch-bound from the host
 
@@ -295,7 +297,18 @@ class BLIP_NLVR(_EngineHost):
         e = NlvrEngine(sd, self.bert_geometry, self.compute_dtype, self.device, fold_merge=self.fold_merge and self.compute_dtype != torch.float32,
                        stream_dtype=self.stream_dtype, cross_dtype=self.token_dtype, split3=self.text_split3 if self.precision == "text32" else 0)
         e.stream32_from = self.text_stream32_from
+        e.fold_long = self.long_caption_fold
         return e
+
+    def set_long_caption_fold(self, on: bool = True):
+        """Captions of 33-64 tokens (the reference tokenises with padding='longest' and no 32-token cut, blip_stage2.py:113; FashionIQ joins two
+        captions) against at most 224 image tokens: run the cross-attention of fusion layers 0-10 through the long-caption query-side fold
+        (cir_cross_attention_folded_long) instead of the projected K|V path.  Off by default; `NlvrEngine.fold_fallbacks` stays at 0 for such
+        batches when it is on.  The setting lives on the model and is re-applied to every engine packed from it."""
+        self.long_caption_fold = bool(on)
+        if self._engines is not None:
+            self._engines[1].fold_long = self.long_caption_fold
+        return self
 
     def _vit_engine(self, sd) -> VitEngine:
         return VitEngine(sd, self.vit_geometry, self.token_dtype, self.device, stream_dtype=self.vit_stream_dtype)

@@ -336,6 +336,11 @@ class NlvrEngine:
         # counts those calls - the kernels' 48-row-per-wave tiling would run them as two passes, which the projected path beats below ~56 tokens).
         self.fold_cross_kv = xdt != torch.float32 and geo.hidden_size == 768 and geo.encoder_width == 768 and geo.num_attention_heads == 12
         self.fold_fallbacks = 0      # forward calls whose captions (> 32 tokens) took the projected path although the fold is on: visible, not silent
+        # Captions of 33 .. 64 tokens against at most 224 keys: with `fold_long` on they take cir_cross_attention_folded_long (one head and up to
+        # three 16-token blocks per wave; cost in 16-token steps) instead of the projected path, and `fold_fallbacks` does not move.  Off by default:
+        # it measures faster than the projected path at 33-48 tokens and slower at 49-64 (LABNOTES.md section 14); a default per length is a later
+        # change (BLIP_NLVR.set_long_caption_fold).
+        self.fold_long = False
         e = prefix + "embeddings."
         self.word, self.posemb = _f32(sd[e + "word_embeddings.weight"], device), _f32(sd[e + "position_embeddings.weight"], device)
         self.ge, self.be = _f32(sd[e + "LayerNorm.weight"], device), _f32(sd[e + "LayerNorm.bias"], device)
@@ -457,7 +462,7 @@ class NlvrEngine:
         graphs = self.__dict__.setdefault("_graphs", {})
         z_t32 = z_t32.float().contiguous()
         key = (tuple(input_ids.shape), tuple(cand16.shape), cand16.dtype, self.kv_chunk, self.trim_last, self.fold_cls_kv, self.fold_cross_kv,
-               getattr(self, "stream32_from", None))
+               getattr(self, "stream32_from", None), self.fold_long)
         g = graphs.pop(key, None)
         if g is None:
             if len(graphs) >= 8:
@@ -551,13 +556,17 @@ class NlvrEngine:
             elif (kv_bank is None and self.fold_cross_kv and "wkt" in ly and not cls_only and l <= 32 and n <= 608
                   and cand16.shape[2] == d):
                 ops.cross_attention_folded(qraw, cand16, ly["wkt"], ly["wvp"], ly["bvf"], ccl, l, scale, heads=geo.num_attention_heads, mask=emask2d)
+            elif (kv_bank is None and self.fold_long and self.fold_cross_kv and "wkt" in ly and not cls_only and 33 <= l <= 64 and n <= 224
+                  and cand16.shape[2] == d):
+                ops.cross_attention_folded_long(qraw, cand16, ly["wkt"], ly["wvp"], ly["bvf"], ccl, l, scale, heads=geo.num_attention_heads, mask=emask2d)
             elif kv_bank is None:
                 if self.fold_cross_kv and "wkt" in ly and l > 32 and i == 1:
                     self.fold_fallbacks += 1
                     if self.fold_fallbacks == 1:
                         import warnings
                         warnings.warn(f"captions of {l} tokens (> 32): the cross-attention runs the projected K|V path for this batch (~8 % of a step slower than "
-                                      "the query-side fold at 224 px); NlvrEngine.fold_fallbacks counts such calls", stacklevel=3)
+                                      "the query-side fold at 224 px); NlvrEngine.fold_fallbacks counts such calls; 33-64 tokens against <= 224 keys can take the "
+                                      "long-caption fold instead: BLIP_NLVR.set_long_caption_fold()", stacklevel=3)
                 # K|V projection + cross-attention, optionally in candidate chunks (`kv_chunk`; measured: no gain from
                 # keeping a chunk's K|V in the Infinity Cache, so the default is one launch each)
                 step_c = self.kv_chunk if self.kv_chunk > 0 else t_n

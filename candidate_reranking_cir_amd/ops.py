@@ -483,10 +483,9 @@ def fold_pack_value(wv: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 4, 2, 1, 6, 3, 5, 7).contiguous().view(b, d, d)          # [b][unit][db][head][g][i][half][r]: j = 4 half + r
 
 
-def cross_attention_folded(q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, wvp: torch.Tensor, bv: torch.Tensor, out: torch.Tensor, l: int,
-                           scale: float, heads: int = 12, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Folded two-branch cross-attention (cir_cross_attention_folded): q (2, T*L, D) cross-query projection, x (T, N, D) tokens, wkt (2, D, D) =
-    fold_pack_key(key.weight), wvp (2, D, D) = fold_pack_value(value.weight), bv (2, D) fp32 -> out (T, L, 2, D) view (written, returned)."""
+def _cross_attention_folded(entry: str, q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, wvp: torch.Tensor, bv: torch.Tensor, out: torch.Tensor, l: int,
+                            scale: float, heads: int, mask: Optional[torch.Tensor]) -> torch.Tensor:
+    """The marshalling and the PROFILE_ATTN record that the two folded entry points share (same parameter list, include/cirrank.h)."""
     _need_cuda(q, x, wkt, wvp, bv, out)
     t_n, n, d = x.shape
     assert q.shape == (2, t_n * l, d) and q.stride(2) == 1 and x.stride(2) == 1 and x.stride(1) == d
@@ -496,15 +495,29 @@ def cross_attention_folded(q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, 
         _need_cuda(mask)
         assert mask.dtype == torch.float32 and mask.shape == (t_n, n) and mask.stride(1) == 1
     ev = _events() if PROFILE_ATTN is not None else None
-    code = _lib.load().cir_cross_attention_folded(q.data_ptr(), q.stride(0), q.stride(1), x.data_ptr(), x.stride(0), wkt.data_ptr(), wvp.data_ptr(), d * d,
-                                                  bv.data_ptr(), _ptr(mask), mask.stride(0) if mask is not None else 0,
-                                                  out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), t_n, l, n, d, heads,
-                                                  float(scale), _DT[x.dtype], _stream())
+    code = getattr(_lib.load(), entry)(q.data_ptr(), q.stride(0), q.stride(1), x.data_ptr(), x.stride(0), wkt.data_ptr(), wvp.data_ptr(), d * d,
+                                       bv.data_ptr(), _ptr(mask), mask.stride(0) if mask is not None else 0,
+                                       out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), t_n, l, n, d, heads,
+                                       float(scale), _DT[x.dtype], _stream())
     if ev is not None:
         ev[1].record()    # executed flops: per (candidate, branch) 2 x (H L x 64 x D) projections + 2 x (H L x D x N) products
         PROFILE_ATTN.append((2.0 * t_n * 2 * (2 * heads * l * 64 * d + 2 * heads * l * d * n), *ev, ("folded", l, n)))
-    _lib.check(code, "cir_cross_attention_folded")
+    _lib.check(code, entry)
     return out
+
+
+def cross_attention_folded(q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, wvp: torch.Tensor, bv: torch.Tensor, out: torch.Tensor, l: int,
+                           scale: float, heads: int = 12, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Folded two-branch cross-attention (cir_cross_attention_folded): q (2, T*L, D) cross-query projection, x (T, N, D) tokens, wkt (2, D, D) =
+    fold_pack_key(key.weight), wvp (2, D, D) = fold_pack_value(value.weight), bv (2, D) fp32 -> out (T, L, 2, D) view (written, returned)."""
+    return _cross_attention_folded("cir_cross_attention_folded", q, x, wkt, wvp, bv, out, l, scale, heads, mask)
+
+
+def cross_attention_folded_long(q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, wvp: torch.Tensor, bv: torch.Tensor, out: torch.Tensor, l: int,
+                                scale: float, heads: int = 12, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cross_attention_folded for captions of up to 64 tokens against up to 224 keys (cir_cross_attention_folded_long): the same operands and
+    packed weights; the cost grows with the caption in 16-token steps."""
+    return _cross_attention_folded("cir_cross_attention_folded_long", q, x, wkt, wvp, bv, out, l, scale, heads, mask)
 
 
 def embed_layernorm(ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,

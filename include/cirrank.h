@@ -244,6 +244,18 @@ int cir_cross_attention_folded(const void* q, int64_t q_sb, int64_t q_rs, const 
                                int T, int L, int N, int D, int H, float scale, int dtype, void* stream);
 
 /*
+ * cir_cross_attention_folded for captions of up to 64 tokens (csrc/xattn_fold_long.hip; additive within ABI v15): the same operator
+ * (nlvr_encoder.py:150-168, 183-217), the same operands, packed weights, key mask and strides, for the captions the reference does not cut at 32
+ * tokens (blip_stage2.py:113: padding='longest', no max_length; FashionIQ joins two captions per query).  D = 768, H = 12, L <= 64, N <= 224
+ * (CIR_ESHAPE otherwise: use cir_gemm_bias_act + cir_attention).  A wave owns one head and up to three 16-token blocks of it; the cost grows in
+ * 16-token steps (12 ceil(L / 16) blocks per candidate and branch).  A row's result does not depend on T, on the candidate's place in the batch or
+ * on L: every block assignment accumulates in one order.
+ */
+int cir_cross_attention_folded_long(const void* q, int64_t q_sb, int64_t q_rs, const void* x, int64_t x_s1, const void* wkt, const void* wvp, int64_t w_sb,
+                                    const float* bv, const float* key_mask, int64_t mask_stride, void* out, int64_t o_st, int64_t o_sr, int64_t o_sb,
+                                    int T, int L, int N, int D, int H, float scale, int dtype, void* stream);
+
+/*
  * BertEmbeddings.forward (nlvr_encoder.py:68-91, med.py:87-110):
  *   y[r] = LayerNorm(word[ids[r]] + pos[r % L]) for r < rows; fp32 tables, outputs as cir_layernorm
  *   (y_stream in CIR_F32 / CIR_F16, y16 in dtype16).
