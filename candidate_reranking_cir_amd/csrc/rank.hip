@@ -1,0 +1,253 @@
+// Stage-I retrieval over an index of any size: the first k columns of every row's descending order (cir_topk_select) and the place of
+// a few given columns in that order (cir_rank_of) - what stage II reads of a full ranking (validate.py:57-64, 202-226), without the
+// 8192-column ceiling of cir_topk_desc's one-row-per-workgroup sort.
+//
+// The order is topk_desc_kernel's (misc.hip): a before b <=> a.val > b.val, or equal values and a.idx < b.idx; a NaN reads as -inf; an
+// excluded column does not exist.  That order is strict and total, so "the first k of a row" is one well-defined list and
+//   first_k(row) = first_k(union over segments of first_k(segment))
+// holds exactly - ties across segment seams, NaNs, +-inf and exclusions included.  Level 1 sorts each segment of at most 8192 columns in
+// LDS and keeps its first k (value, column) pairs; level 2 sorts groups of floor(8192 / k) such lists the same way until one is left.
+// Lists are always k pairs long: missing places hold the padding pair (-inf, INT_MAX), which comes after every real column (columns are
+// below 2^31 - 1) and never reaches the result, because k <= n - 1 real columns exist in every row.
+#include "common.hpp"
+
+namespace cir {
+
+constexpr int RANK_SEG = 8192;                  // pairs per workgroup sort: 64 KiB of LDS
+constexpr int RANK_PAD = 0x7fffffff;
+
+struct __attribute__((aligned(8))) RankPair { float v; int i; };
+
+__device__ __forceinline__ bool rank_before(float va, int ia, float vb, int ib) { return (va > vb) || (va == vb && ia < ib); }
+__device__ __forceinline__ float rank_key(float v) { return v != v ? -INFINITY : v; }   // NaN sorts last
+
+// The first `first` places of the sorted order, in place (first: a power of two, 2 <= first <= n_pow2; every thread of the workgroup calls it).
+// Phase 1 is the bitonic network of topk_desc_kernel on interleaved pairs (one 8-byte LDS access per pair), stopped at runs of `first`: they
+// come out alternately descending and ascending.  Phase 2 halves the number of runs until one is left: a descending run and its ascending
+// neighbour form a bitonic sequence, so the pairwise winners (place i against place i, `span` apart) are the `first` leading pairs of the two
+// runs and bitonic again; one merge pass (strides first / 2 .. 1) sorts them, descending or ascending by the run's new number.  Only winners
+// are kept, so a segment of 8192 costs 28 + 6 * 8 steps at first = 128, all but the first 28 on a shrinking part, against 91 full ones.
+__device__ __forceinline__ void rank_sort_first(RankPair* p, int n_pow2, int first) {
+    for (int size = 2; size <= first; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < n_pow2 / 2; t += blockDim.x) {
+                const int lo = 2 * t - (t & (stride - 1));
+                const int hi = lo + stride;
+                const bool asc_block = ((lo & size) != 0);
+                const RankPair a = p[lo], b = p[hi];
+                const bool a_first = rank_before(a.v, a.i, b.v, b.i);
+                if (asc_block ? a_first : !a_first) { p[lo] = b; p[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    const int lg = __ffs(first) - 1;
+    for (int span = first; span < n_pow2;) {
+        for (int t = threadIdx.x; t < (n_pow2 / (2 * span)) * first; t += blockDim.x) {
+            const int lo = (t >> lg) * 2 * span + (t & (first - 1));
+            const RankPair a = p[lo], b = p[lo + span];
+            if (!rank_before(a.v, a.i, b.v, b.i)) p[lo] = b;          // the loser's run is not read again
+        }
+        __syncthreads();
+        span <<= 1;
+        for (int stride = first >> 1; stride > 0; stride >>= 1) {
+            for (int t = threadIdx.x; t < (n_pow2 / span) * (first >> 1); t += blockDim.x) {
+                const int run = t >> (lg - 1), u = t & ((first >> 1) - 1);
+                const int lo = run * span + 2 * u - (u & (stride - 1));
+                const int hi = lo + stride;
+                const RankPair a = p[lo], b = p[hi];
+                const bool a_first = rank_before(a.v, a.i, b.v, b.i);
+                if ((run & 1) ? a_first : !a_first) { p[lo] = b; p[hi] = a; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// the first k sorted pairs: to a k-pair list of the workspace, or - the last level - to the result rows
+__device__ __forceinline__ void rank_emit(const RankPair* p, int n_pow2, int k, RankPair* list, int64_t* idx, float* val) {
+    for (int j = threadIdx.x; j < k; j += blockDim.x) {
+        RankPair e;
+        if (j < n_pow2) e = p[j]; else { e.v = -INFINITY; e.i = RANK_PAD; }
+        if (list != nullptr) list[j] = e;
+        else { idx[j] = e.i; if (val != nullptr) val[j] = e.v; }
+    }
+}
+
+// ---- level 1: one workgroup per (row, segment); blockIdx.x = row * segs + segment ----
+__global__ __launch_bounds__(1024) void topk_segment_kernel(const float* __restrict__ values, int64_t ld, const int64_t* __restrict__ exclude, int n, int k,
+                                                            int segs, RankPair* __restrict__ lists, int64_t* __restrict__ idx, float* __restrict__ val) {
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    RankPair* p = reinterpret_cast<RankPair*>(dyn);
+    const int64_t row = blockIdx.x / (unsigned)segs;
+    const int seg = (int)(blockIdx.x - row * segs);
+    const int c0 = seg * RANK_SEG;                      // < n
+    const int len = min(n - c0, RANK_SEG);
+    int n_pow2 = 2, keep = 2;
+    while (n_pow2 < len) n_pow2 <<= 1;
+    while (keep < k) keep <<= 1;
+    const int64_t ex = exclude != nullptr ? exclude[row] : -1;
+    const float* src = values + row * ld + c0;
+    for (int i = threadIdx.x; i < n_pow2; i += blockDim.x) {
+        RankPair e;
+        if (i < len && (int64_t)(c0 + i) != ex) { e.v = rank_key(src[i]); e.i = c0 + i; }
+        else { e.v = -INFINITY; e.i = RANK_PAD; }
+        p[i] = e;
+    }
+    __syncthreads();
+    rank_sort_first(p, n_pow2, min(keep, n_pow2));
+    if (lists != nullptr) rank_emit(p, n_pow2, k, lists + (int64_t)blockIdx.x * k, nullptr, nullptr);
+    else rank_emit(p, n_pow2, k, nullptr, idx + row * k, val != nullptr ? val + row * k : nullptr);
+}
+
+// ---- level 2: one workgroup per (row, group of at most `group` lists); blockIdx.x = row * lists_out + g; group * k <= 8192 ----
+__global__ __launch_bounds__(1024) void topk_merge_kernel(const RankPair* __restrict__ in, int lists_in, int group, int lists_out, int k,
+                                                          RankPair* __restrict__ out, int64_t* __restrict__ idx, float* __restrict__ val) {
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    RankPair* p = reinterpret_cast<RankPair*>(dyn);
+    const int64_t row = blockIdx.x / (unsigned)lists_out;
+    const int g = (int)(blockIdx.x - row * lists_out);
+    const int first = g * group;
+    const int cnt = min(group, lists_in - first) * k;
+    int n_pow2 = 2, keep = 2;
+    while (n_pow2 < cnt) n_pow2 <<= 1;
+    while (keep < k) keep <<= 1;
+    const RankPair* src = in + (row * lists_in + first) * k;
+    for (int i = threadIdx.x; i < n_pow2; i += blockDim.x) {
+        RankPair e;
+        if (i < cnt) e = src[i]; else { e.v = -INFINITY; e.i = RANK_PAD; }
+        p[i] = e;
+    }
+    __syncthreads();
+    rank_sort_first(p, n_pow2, min(keep, n_pow2));
+    if (out != nullptr) rank_emit(p, n_pow2, k, out + (int64_t)blockIdx.x * k, nullptr, nullptr);
+    else rank_emit(p, n_pow2, k, nullptr, idx + row * k, val != nullptr ? val + row * k : nullptr);
+}
+
+// (value, column) -> one unsigned 64-bit word whose integer order is the order above: a before b <=> rank_word(a) > rank_word(b).  High half: the
+// key's bits made monotone (-0 joins +0, as the float compare has them equal); low half: INT_MAX - column, so the lower column is the larger word.
+__device__ __forceinline__ unsigned long long rank_word(float v, int col) {
+    v = rank_key(v);
+    if (v == 0.f) v = 0.f;
+    const unsigned u = __float_as_uint(v);
+    const unsigned hi = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)hi << 32) | (unsigned)(RANK_PAD - col);
+}
+
+// ---- rank[q][t] = number of columns of row q that come before column cols[q][t]; one workgroup per row, one pass, integer counts ----
+__global__ __launch_bounds__(256) void rank_of_kernel(const float* __restrict__ values, int64_t ld, const int64_t* __restrict__ cols,
+                                                      const int64_t* __restrict__ exclude, int64_t* __restrict__ rank, int n, int m) {
+    __shared__ int part[4][8];
+    const int64_t row = blockIdx.x;
+    const float* r = values + row * ld;
+    int64_t ex = exclude != nullptr ? exclude[row] : -1;
+    if (ex < 0 || ex >= n) ex = -1;
+    unsigned long long kw[8];
+    int cnt[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int64_t c = t < m ? cols[row * m + t] : -1;
+        const bool valid = c >= 0 && c < n && c != ex;
+        kw[t] = valid ? rank_word(r[c], (int)c) : ~0ull;   // no word is above ~0: an invalid column counts nothing
+        cnt[t] = 0;
+    }
+    auto count = [&](float v, int j) {
+        const unsigned long long w = rank_word(v, j);
+#pragma unroll
+        for (int t = 0; t < 8; ++t) cnt[t] += w > kw[t] ? 1 : 0;
+    };
+    // scalar head up to the row's first 16-byte boundary, float4 body, scalar tail (rows of a strided view start anywhere)
+    const int head = min(n, (int)((4 - ((reinterpret_cast<uintptr_t>(r) >> 2) & 3)) & 3));
+    const int nvec = (n - head) >> 2;
+    if ((int)threadIdx.x < head) count(r[threadIdx.x], threadIdx.x);
+    const float4* r4 = reinterpret_cast<const float4*>(r + head);
+    for (int i = threadIdx.x; i < nvec; i += 256) {
+        const float4 v = r4[i];
+        const int j = head + 4 * i;
+        count(v.x, j); count(v.y, j + 1); count(v.z, j + 2); count(v.w, j + 3);
+    }
+    const int tail0 = head + 4 * nvec;
+    if ((int)threadIdx.x < n - tail0) count(r[tail0 + threadIdx.x], tail0 + threadIdx.x);
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt[t] += __shfl_xor(cnt[t], o, 64);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][t] = cnt[t];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < m) {
+        const int t = threadIdx.x;
+        const int64_t c = cols[row * m + t];
+        const bool valid = c >= 0 && c < n && c != ex;
+        int total = part[0][t] + part[1][t] + part[2][t] + part[3][t];   // fixed order (and integers)
+        if (valid && ex >= 0 && rank_word(r[ex], (int)ex) > rank_word(r[c], (int)c)) total -= 1;   // the excluded column was counted
+        rank[row * m + t] = valid ? (int64_t)total : -1;
+    }
+}
+
+struct RankPlan { int segs, group; int64_t bytes_a, bytes_b; };
+
+// the extents' checks and the workspace layout shared by the three entry points: list buffer A (Q * segs lists of k pairs, level 1's
+// output) and, above one segment, buffer B (Q * ceil(segs / group) lists); the merge rounds alternate between the two
+static int rank_plan(int64_t Q, int64_t n, int64_t k, RankPlan* plan) {
+    if (Q <= 0 || n <= 0 || k <= 0) return CIR_EINVAL;
+    if (k > 2048 || k > n - 1 || n > 0x7fffffffLL) return CIR_ESHAPE;
+    const int64_t segs = (n + RANK_SEG - 1) / RANK_SEG;
+    if (Q * segs > 0x7fffffffLL) return CIR_ESHAPE;      // one grid dimension over (row, segment)
+    plan->segs = (int)segs;
+    plan->group = (int)(RANK_SEG / k);
+    plan->bytes_a = Q * segs * k * (int64_t)sizeof(RankPair);
+    plan->bytes_b = segs > 1 ? Q * ((segs + plan->group - 1) / plan->group) * k * (int64_t)sizeof(RankPair) : 0;
+    return CIR_OK;
+}
+
+static int rank_pow2(int n) { int p = 2; while (p < n) p <<= 1; return p; }
+
+}  // namespace cir
+
+extern "C" int64_t cir_topk_select_workspace(int Q, int n, int k) {
+    cir::RankPlan plan;
+    const int code = cir::rank_plan(Q, n, k, &plan);
+    return code != CIR_OK ? (int64_t)code : plan.bytes_a + plan.bytes_b;
+}
+
+extern "C" int cir_topk_select(const float* values, int64_t ld, const int64_t* exclude, int64_t* idx, float* val, int Q, int n, int k,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+    using namespace cir;
+    CIR_CHECK_PTR(values); CIR_CHECK_PTR(idx);
+    if (ld < n) return CIR_EINVAL;
+    RankPlan plan;
+    const int code = rank_plan(Q, n, k, &plan);
+    if (code != CIR_OK) return code;
+    if (workspace == nullptr || workspace_bytes < plan.bytes_a + plan.bytes_b) return CIR_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int seg_pow2 = rank_pow2(n < RANK_SEG ? n : RANK_SEG);
+    RankPair* buf_a = reinterpret_cast<RankPair*>(workspace);
+    RankPair* buf_b = reinterpret_cast<RankPair*>(reinterpret_cast<char*>(workspace) + plan.bytes_a);
+    {
+        dim3 grid((unsigned)((int64_t)Q * plan.segs)), block(seg_pow2 >= 2048 ? 1024 : 256);
+        hipLaunchKernelGGL(topk_segment_kernel, grid, block, (size_t)seg_pow2 * sizeof(RankPair), s, values, ld, exclude, n, k, plan.segs,
+                           plan.segs > 1 ? buf_a : nullptr, idx, val);
+    }
+    RankPair *in = buf_a, *out = buf_b;
+    for (int lists = plan.segs; lists > 1;) {
+        const int lists_out = (lists + plan.group - 1) / plan.group;
+        const int pow2 = rank_pow2((lists < plan.group ? lists : plan.group) * k);
+        dim3 grid((unsigned)((int64_t)Q * lists_out)), block(pow2 >= 2048 ? 1024 : 256);
+        hipLaunchKernelGGL(topk_merge_kernel, grid, block, (size_t)pow2 * sizeof(RankPair), s, in, lists, plan.group, lists_out, k,
+                           lists_out > 1 ? out : nullptr, idx, val);
+        RankPair* t = in; in = out; out = t;
+        lists = lists_out;
+    }
+    CIR_LAUNCH_RESULT();
+}
+
+extern "C" int cir_rank_of(const float* values, int64_t ld, const int64_t* cols, const int64_t* exclude, int64_t* rank, int Q, int n, int m,
+                           void* stream) {
+    CIR_CHECK_PTR(values); CIR_CHECK_PTR(cols); CIR_CHECK_PTR(rank);
+    if (Q <= 0 || n <= 0 || m <= 0 || ld < n) return CIR_EINVAL;
+    if (m > 8) return CIR_ESHAPE;
+    dim3 grid((unsigned)Q), block(256);
+    hipLaunchKernelGGL(cir::rank_of_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), values, ld, cols, exclude, rank, n, m);
+    CIR_LAUNCH_RESULT();
+}

@@ -590,6 +590,51 @@ def argsort_desc(logits: torch.Tensor) -> torch.Tensor:
     return idx
 
 
+def _rank_rows(values: torch.Tensor, exclude: Optional[torch.Tensor]):
+    """The fp32 (Q, n) operand of cir_topk_select / cir_rank_of as it stands where its rows are unit-stride and at least n apart (a
+    `[:, :n]` view of a wider buffer), a contiguous copy otherwise; `exclude` as int64 (Q,)."""
+    _need_cuda(values, exclude)
+    assert values.dim() == 2 and values.dtype == torch.float32 and values.shape[0] < 2 ** 31 and values.shape[1] < 2 ** 31
+    if values.stride(1) != 1 or values.stride(0) < values.shape[1]:
+        values = values.contiguous()
+    if exclude is not None:
+        exclude = exclude.to(torch.int64).contiguous()
+        assert exclude.shape == (values.shape[0],)
+    return values, exclude
+
+
+def topk_desc(values: torch.Tensor, k: int, exclude: Optional[torch.Tensor] = None, return_values: bool = False):
+    """The first k columns of every row's descending order - argsort_desc's order exactly (ties -> lower index, NaN = -inf), for rows of any
+    length (cir_topk_select): (Q, k) int64, with `return_values` also the (Q, k) fp32 keys as sorted.  `exclude` (Q,) int64: one column per row
+    that does not exist (-1: none).  1 <= k <= min(2048, n - 1)."""
+    values, exclude = _rank_rows(values, exclude)
+    q, n = values.shape
+    c = _lib.load()
+    need = c.cir_topk_select_workspace(q, n, k)
+    if need < 0:
+        _lib.check(int(need), "cir_topk_select_workspace")
+    work = torch.empty(need, dtype=torch.uint8, device=values.device)
+    idx = torch.empty((q, k), dtype=torch.int64, device=values.device)
+    val = torch.empty((q, k), dtype=torch.float32, device=values.device) if return_values else None
+    code = c.cir_topk_select(values.data_ptr(), values.stride(0), _ptr(exclude), idx.data_ptr(), _ptr(val), q, n, k, work.data_ptr(), need, _stream())
+    _lib.check(code, "cir_topk_select")
+    return (idx, val) if return_values else idx
+
+
+def rank_of(values: torch.Tensor, cols: torch.Tensor, exclude: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(Q, m <= 8) int64: the position of column cols[q, t] in row q's descending order (the order of topk_desc, `exclude` included): the
+    number of columns that come before it; -1 for a column outside the row or equal to the excluded one (cir_rank_of)."""
+    values, exclude = _rank_rows(values, exclude)
+    _need_cuda(cols)
+    cols = cols.to(torch.int64).contiguous()
+    q, n = values.shape
+    assert cols.dim() == 2 and cols.shape[0] == q
+    rank = torch.empty_like(cols)
+    code = _lib.load().cir_rank_of(values.data_ptr(), values.stride(0), cols.data_ptr(), _ptr(exclude), rank.data_ptr(), q, n, cols.shape[1], _stream())
+    _lib.check(code, "cir_rank_of")
+    return rank
+
+
 def gather_rows(src: torch.Tensor, index: Optional[torch.Tensor], dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """dst[i] = src[index[i]] converted to `dtype`; rows are src.shape[1:] flattened (index None = plain convert)."""
     _need_cuda(src, index)

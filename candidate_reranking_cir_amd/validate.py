@@ -56,6 +56,33 @@ def rank_index(predicted: torch.Tensor, index_pooled: torch.Tensor) -> torch.Ten
     return ops.argsort_desc(neg_dist)                                    # ascending distance; ties -> lower index
 
 
+@torch.no_grad()
+def rank_index_topk(predicted: torch.Tensor, index_pooled: torch.Tensor, k: int, exclude=None, cols=None, row_block: Optional[int] = None):
+    """What stage II reads of `rank_index`'s ranking, for an index of any size: (topk (Q, k) int64, ranks (Q, m) int64 or None).
+    `topk` holds the first k columns of each row of `rank_index(predicted, index_pooled)` - with column `exclude[q]` removed from row q
+    first, where given (CIRR drops the reference image, validate.py:207-210) -, `ranks[q, t]` the position of index row `cols[q, t]` in that
+    ranking (m <= 8; -1 for the excluded row).  The distance matrix comes from the same `ops.linear_f32` call as `rank_index`'s, `row_block`
+    query rows at a time (default: tiles of at most 1 GiB), so its bits and therefore the order are `rank_index`'s wherever both run; no row is
+    sorted (ops.topk_desc, ops.rank_of), and `n_index` has no ceiling."""
+    index = index_pooled.contiguous()
+    q_n, n_idx = predicted.shape[0], index.shape[0]
+    dev = predicted.device
+    if row_block is None:
+        row_block = max(1, min((1 << 30) // (4 * n_idx), 65535 * 64))
+    exclude = None if exclude is None else torch.as_tensor(exclude, dtype=torch.int64, device=dev)
+    cols = None if cols is None else torch.as_tensor(cols, dtype=torch.int64, device=dev).reshape(q_n, -1)
+    topk = torch.empty((q_n, k), dtype=torch.int64, device=dev)
+    ranks = None if cols is None else torch.empty_like(cols)
+    for s in range(0, q_n, row_block):
+        rows = slice(s, min(s + row_block, q_n))
+        neg_dist = ops.linear_f32(predicted[rows], index, None, mode=2)     # rank_index's matrix, a tile of it
+        ex = None if exclude is None else exclude[rows]
+        topk[rows] = ops.topk_desc(neg_dist, k, ex)
+        if cols is not None:
+            ranks[rows] = ops.rank_of(neg_dist, cols[rows], ex)
+    return topk, ranks
+
+
 def recall_at(labels: np.ndarray, k: int) -> float:
     lab = torch.tensor(labels)
     return (torch.sum(lab[:, :k]) / len(lab)).item() * 100
@@ -87,6 +114,58 @@ def cirr_topk(sorted_rows: np.ndarray, ref_index: np.ndarray, target_index: np.n
                index_names=list(index_names), labels=torch.tensor(labels[:, :k]), group_labels=torch.tensor(group_labels), split=split)
     metrics = (recall_at(group_labels, 1), recall_at(group_labels, 2), recall_at(group_labels, 3),
                recall_at(labels, 1), recall_at(labels, 5), recall_at(labels, 10), recall_at(labels, 50))
+    return metrics, top
+
+
+def _recall_of_ranks(rank: np.ndarray, k: int) -> float:
+    """recall_at(labels, k) of the full label matrix whose one positive of row q sits at column rank[q]."""
+    return recall_at((rank < k)[:, None], 1)
+
+
+def fiq_topk_from_ranks(topk: np.ndarray, target_rank: np.ndarray, target_index: np.ndarray, index_names: List[str], k: int, split: str,
+                        dress_type: str):
+    """`fiq_topk` from `rank_index_topk(pred, pooled, k, cols=target_index[:, None])` instead of a full ranking: the same metrics tuple and
+    the same top-K dict.  The reference's "one positive per row" (validate.py:64) is the target's rank lying inside the row."""
+    topk, target_index = np.asarray(topk), np.asarray(target_index)
+    rank = np.asarray(target_rank).reshape(len(topk))
+    assert topk.shape[1] >= k and ((rank >= 0) & (rank < len(index_names))).all()       # validate.py:64
+    labels = np.arange(k)[None, :] == rank[:, None]
+    assert (topk[:, :k][labels] == target_index[labels.any(1)]).all()                   # the column at the target's rank is the target
+    names = np.array(index_names)
+    top = dict(sorted_index_names=names[topk[:, :k]], target_names=[index_names[i] for i in target_index],
+               index_names=list(index_names), labels=torch.tensor(labels), split=split, dress_types=dress_type)
+    return (_recall_of_ranks(rank, 10), _recall_of_ranks(rank, 50)), top
+
+
+def cirr_rank_cols(ref_index: np.ndarray, target_index: np.ndarray, group_index: np.ndarray) -> np.ndarray:
+    """(Q, 6) index rows whose ranks `cirr_topk_from_ranks` reads: [target | the 5 group members besides the reference]; pass it as `cols`
+    and `ref_index` as `exclude` to `rank_index_topk`.  `group_index` (Q, 6) holds the full groups incl. the reference, as in the dataset."""
+    ref_index, group_index = np.asarray(ref_index), np.asarray(group_index)
+    keep = group_index != ref_index[:, None]
+    assert (keep.sum(1) == group_index.shape[1] - 1).all()                              # the reference is one member of its group
+    return np.concatenate([np.asarray(target_index)[:, None], group_index[keep].reshape(len(group_index), -1)], axis=1).astype(np.int64)
+
+
+def cirr_topk_from_ranks(topk: np.ndarray, ranks: np.ndarray, ref_index: np.ndarray, target_index: np.ndarray, group_index: np.ndarray,
+                         index_names: List[str], k: int, split: str):
+    """`cirr_topk` from `rank_index_topk(pred, pooled, k, exclude=ref_index, cols=cirr_rank_cols(...))` instead of a full ranking: the same 7
+    metrics and the same top-K dict, `group_labels (Q, 5)` included (group_labels[q, j]: the j-th group member by rank is the target).  The
+    reference's asserts (validate.py:225-226) become: the target's rank lies inside the row, and the target is one of its group's members."""
+    topk, ranks, target_index = np.asarray(topk), np.asarray(ranks), np.asarray(target_index)
+    members = cirr_rank_cols(ref_index, target_index, group_index)[:, 1:]
+    rank, group_rank = ranks[:, 0], ranks[:, 1:]
+    assert topk.shape[1] >= k and ranks.shape == (len(topk), 1 + members.shape[1])
+    assert ((rank >= 0) & (rank < len(index_names) - 1)).all() and (group_rank >= 0).all()
+    labels = np.arange(k)[None, :] == rank[:, None]
+    assert (topk[:, :k][labels] == target_index[labels.any(1)]).all()
+    by_rank = np.take_along_axis(members, np.argsort(group_rank, axis=1, kind="stable"), axis=1)
+    group_labels = by_rank == target_index[:, None]
+    assert (group_labels.sum(1) == 1).all()                                             # validate.py:225-226
+    names = np.array(index_names)
+    top = dict(sorted_index_names=names[topk[:, :k]], target_names=[index_names[i] for i in target_index],
+               index_names=list(index_names), labels=torch.tensor(labels), group_labels=torch.tensor(group_labels), split=split)
+    metrics = (recall_at(group_labels, 1), recall_at(group_labels, 2), recall_at(group_labels, 3),
+               _recall_of_ranks(rank, 1), _recall_of_ranks(rank, 5), _recall_of_ranks(rank, 10), _recall_of_ranks(rank, 50))
     return metrics, top
 
 

@@ -305,6 +305,31 @@ int cir_gather_rows(const void* src, int src_dtype, const int64_t* index, void* 
 int cir_topk_desc(const float* logits, int64_t* idx, int Q, int K, void* stream);
 
 /*
+ * Stage-I retrieval over an index of ANY size (csrc/rank.hip; three entry points, additive within ABI v15 like cir_cross_attention_folded_long):
+ * what stage II reads of a full ranking - the first k columns of every row (validate.py:57-64: sorted_index_names[:, :k]) and the place of the
+ * target and of the CIRR group members (validate.py:202-226) - without sorting the row.  The order is cir_topk_desc's, exactly: a before b
+ * <=> a.val > b.val, or equal values and a.idx < b.idx; a NaN reads as -inf; an excluded column does not exist (CIRR drops the reference
+ * image from every row, validate.py:207-210).  The order is strict and total, so results are unique and equal cir_topk_desc's wherever both run.
+ *
+ * cir_topk_select (validate.py:57-64, 202-226): values fp32 (Q, n), rows ld >= n elements apart, never written; exclude int64 (Q) or NULL: one
+ *   column per row to drop, -1 = none; idx int64 (Q, k) receives the first k columns of the order; val fp32 (Q, k) or NULL receives their keys as
+ *   sorted (a NaN appears as -inf).  1 <= k <= 2048, k <= n - 1, n < 2^31 (CIR_ESHAPE otherwise).  One workgroup per (row, segment of 8192
+ *   columns) sorts its segment in LDS and keeps its first k pairs; groups of floor(8192 / k) such lists are sorted again until one is left.  Grids
+ *   are one-dimensional over (row, segment): Q * ceil(n / 8192) < 2^31 (CIR_ESHAPE beyond).  No atomics; no workgroup waits for another.
+ *   workspace: a caller-owned device buffer of at least cir_topk_select_workspace(Q, n, k) bytes, 8-byte aligned (CIR_EINVAL when NULL or
+ *   smaller); its contents are scratch.
+ * cir_topk_select_workspace (validate.py:57-64, 202-226): pure host function; the bytes cir_topk_select needs for these extents, or a negative
+ *   CIR_E* code for extents it refuses.
+ * cir_rank_of (validate.py:57-64, 202-226): cols int64 (Q, m), m <= 8 (CIR_ESHAPE beyond); rank int64 (Q, m) receives the number of non-excluded
+ *   columns that come before cols[q][t] in the order above - its position in the ranking, which is what `labels` marks (validate.py:60-64, 213-226);
+ *   -1 for a column outside [0, n) or equal to the row's excluded one.  One pass over the row per workgroup, integer counts, fixed-order reduction.
+ */
+int64_t cir_topk_select_workspace(int Q, int n, int k);
+int cir_topk_select(const float* values, int64_t ld, const int64_t* exclude, int64_t* idx, float* val, int Q, int n, int k,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int cir_rank_of(const float* values, int64_t ld, const int64_t* cols, const int64_t* exclude, int64_t* rank, int Q, int n, int m, void* stream);
+
+/*
  * fp32 y (M,N) = x (M,K) W(N,K)^T + bias (mode 0), 1 - x W^T (mode 1) or x W^T - 1 (mode 2, the exact
  * negative of mode 1, so that cir_topk_desc ranks by ascending distance): stage I's 256-d heads
  * vision_proj / text_proj (blip_stage1.py:42-43, 58, 83) and its distance matrix
