@@ -35,7 +35,8 @@ from typing import Dict, List
 import torch
 
 from . import ops, train_ops as T
-from .train_core import Trainer, _Lin, _Lin2, _cast, _install_grads, _row_split, loss_scale, train_dtype  # noqa: F401  (re-exported)
+from .train_core import (Trainer, _Lin, _Lin2, _cast, _install_grads, _row_split, apply_pending_counters, load_training_state,  # noqa: F401
+                         loss_scale, train_dtype, training_state)                                                             # (re-exported)
 from .train_optim import AdamW, cosine_lr_schedule  # noqa: F401  (re-exported)
 from .train_ops import deterministic, set_deterministic  # noqa: F401  (re-exported: the deterministic training mode)
 
@@ -347,6 +348,7 @@ def fusion_train(model, z_t, feats, ids, mask, p_hidden: float = 0.1, p_attn: fl
     tr = getattr(model, "_trainer", None)
     if tr is None or (tr.p_hidden, tr.p_attn) != (float(p_hidden), float(p_attn)) or tr.dtype != train_dtype(model):
         tr = model._trainer = NlvrTrainer(model, p_hidden, p_attn, seed)
+        apply_pending_counters(model, "fusion", tr)           # (seed, step_no) a checkpoint left for this trainer (load_training_state)
         tr.anchor = torch.zeros((1,), device=z_t.device, requires_grad=True)
     tr.need_dfeats = bool(torch.is_tensor(feats) and feats.requires_grad)
     return _FusionTrainFn.apply(tr.anchor, tr, z_t, feats, ids, mask)

@@ -1,8 +1,8 @@
 """What the hand-written training passes share (train.py: the stage-II two-branch encoder, train_stage1.py: the stage-I MED encoder,
 train_vit.py: ViT fine-tuning; train_med.py: the dropout draw): the flat parameter slab with its 16-bit copy and transposed twin (`_Slab`),
 the layer views over it (`_Lin`, `_Lin2`, `_LN`), the slab order (`slab_order`), the head views of the attention kernels (`head_view`), the
-fp16 loss scale (`loss_scale`), the per-forward dropout seed (`draw_seed`), the installation of flat gradient slices into `.grad`
-(`_install_grads`), and `Trainer`: the per-step packing, the end of a backward and the one-slot guard of the autograd nodes.  A pass module
+fp16 loss scale (`loss_scale`), the per-forward dropout seed (`draw_seed`), the random state a checkpoint carries (`training_state` /
+`load_training_state`), the installation of flat gradient slices into `.grad` (`_install_grads`), and `Trainer`: the per-step packing, the end of a backward and the one-slot guard of the autograd nodes.  A pass module
 keeps its group table, `_trained`, `_build_layers`, `forward`, `backward` and its entry function.
 """
 from __future__ import annotations
@@ -390,6 +390,61 @@ def draw_seed(seed: Optional[int] = None) -> int:
     """The base seed of one forward's dropout sites: `seed`, or one 62-bit draw from torch's global CPU generator (`torch.manual_seed`
     governs it, as it governs the reference's dropout; no device read)."""
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if seed is None else seed
+
+
+# ---- the resumable part of the training state that is neither a parameter nor an optimizer moment ---------------------------------------
+# Two passes number their random draws themselves: train.NlvrTrainer's dropout sites and train_vit.VitTrainer's DropPath draw are functions
+# of the trainer's (seed, step_no).  Everything else that is random in a training-mode pass - `draw_seed` above (the stage-I trainer and the
+# train-mode z_t of train_med.py) and the frozen ViT's DropPath draw (BLIP_NLVR.img_embed) - reads torch's global CPU generator; none reads
+# a device generator.
+_COUNTED = {"fusion": "_trainer", "vit": "_vit_trainer"}     # key in the state -> the model attribute that holds the trainer
+_PENDING = "_pending_counters"                                # counters loaded before their trainer exists (trainers are built lazily)
+
+
+def training_state(model) -> dict:
+    """What a checkpoint needs besides `model.state_dict()` and `AdamW.state_dict()` for the run to continue with the random draws it
+    would have made (BLIP_NLVR and BLIP_Retrieval): the (seed, step_no) of the fusion and the ViT trainer where the model has them (or has
+    them pending from `load_training_state`), and the state of torch's global CPU generator.  Plain values and one uint8 tensor: it sits
+    in the same file and loads under torch.load(weights_only=True)."""
+    state = {"format": 1, "cpu_rng_state": torch.get_rng_state()}
+    pending = getattr(model, _PENDING, None) or {}
+    for key, attr in _COUNTED.items():
+        tr = getattr(model, attr, None)
+        if tr is not None and hasattr(tr, "step_no"):         # (the stage-I trainer keeps no count: it draws from the generator)
+            state[key] = {"seed": int(tr.seed), "step_no": int(tr.step_no)}
+        elif key in pending:
+            state[key] = dict(pending[key])
+    return state
+
+
+def load_training_state(model, state: dict):
+    """Restore `training_state`'s result.  Counters of a trainer that exists are set on it; those of one that does not exist yet - a fresh
+    model builds its trainers at the first training-mode forward - wait on the model until `apply_pending_counters` hands them to the new
+    trainer, once.  A trainer rebuilt after that (other dropout probabilities, other operand type) starts from 0, as ever."""
+    if state.get("format") != 1:
+        raise ValueError(f"load_training_state: format {state.get('format')!r}; this build reads format 1")
+    counters = {key: {"seed": int(state[key]["seed"]), "step_no": int(state[key]["step_no"])} for key in _COUNTED if key in state}
+    rng = state["cpu_rng_state"]
+    pending = {}
+    for key, attr in _COUNTED.items():
+        tr = getattr(model, attr, None)
+        if key not in counters:
+            continue
+        if tr is not None and hasattr(tr, "step_no"):
+            tr.seed, tr.step_no = counters[key]["seed"], counters[key]["step_no"]
+        else:
+            pending[key] = counters[key]
+    setattr(model, _PENDING, pending)
+    torch.set_rng_state(rng.cpu())
+
+
+def apply_pending_counters(model, key: str, trainer):
+    """Called where a counted trainer is constructed (train.fusion_train, train_vit.vit_train): hand it the counters a checkpoint left on
+    the model, and forget them."""
+    pending = getattr(model, _PENDING, None)
+    if pending and key in pending:
+        c = pending.pop(key)
+        trainer.seed, trainer.step_no = c["seed"], c["step_no"]
 
 
 class Trainer:

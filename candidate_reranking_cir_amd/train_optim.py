@@ -1,5 +1,6 @@
 """`AdamW`: torch.optim.AdamW's update rule on cir_adamw_step for the trainers' flat parameter slabs (train_core._Slab), with GradScaler's
-found_inf / skip decision taken on the device; `cosine_lr_schedule`: the reference's per-epoch decay."""
+found_inf / skip decision taken on the device, and torch.optim's `state_dict()` / `load_state_dict()` for the reference's checkpoints
+(utils.save_model); `cosine_lr_schedule`: the reference's per-epoch decay."""
 from __future__ import annotations
 
 import math
@@ -192,3 +193,80 @@ class AdamW:
     def zero_grad(self):
         for p in self.params:
             p.grad = None
+
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    def state_dict(self) -> dict:
+        """torch.optim.AdamW's layout (utils.save_model calls this once per epoch, utils.py:135-150; stage2_train.py:303):
+        {"state": {i: {"step", "exp_avg", "exp_avg_sq"}}, "param_groups": [group]}, i indexing the requires_grad parameters in constructor
+        order.  The moments are the LIVE tensors (on the flat path the views into the slab-sized buffers: torch.save writes each buffer
+        once), `step` the one global count of applied steps as torch writes it (0-d fp32, one tensor per entry: torch increments each in
+        place).  "cir" carries what torch has no slot for; torch.optim ignores it.  Reads the device (the counts live there)."""
+        t = self.t
+        state = {i: {"step": torch.tensor(float(t), dtype=torch.float32), "exp_avg": self.m[id(p)], "exp_avg_sq": self.v[id(p)]}
+                 for i, p in enumerate(self.params) if id(p) in self.m}
+        g = self.param_groups[0]
+        group = {"lr": g["lr"], "betas": tuple(g["betas"]), "eps": g["eps"], "weight_decay": g["weight_decay"], "amsgrad": False,
+                 "maximize": False, "params": list(range(len(self.params)))}
+        return {"state": state, "param_groups": [group], "cir": {"skipped_steps": self.skipped_steps, "format": 1}}
+
+    def _read_state_dict(self, sd):
+        """Validate `sd` against this optimizer without touching it: (group, {i: (exp_avg, exp_avg_sq)}, applied steps, skipped steps).
+        ValueError names the first offender."""
+        groups = sd["param_groups"]
+        if len(groups) != 1:
+            raise ValueError(f"AdamW.load_state_dict: {len(groups)} parameter groups in the state dict; this optimizer has exactly one")
+        group = groups[0]
+        if len(group["params"]) != len(self.params):
+            raise ValueError(f"AdamW.load_state_dict: the saved group has {len(group['params'])} parameters, this optimizer has {len(self.params)}")
+        for flag in ("amsgrad", "maximize"):
+            if group.get(flag, False):
+                raise ValueError(f"AdamW.load_state_dict: the saved group has {flag}=True, which cir_adamw_step does not implement")
+        if group.get("decoupled_weight_decay", True) is False:
+            raise ValueError("AdamW.load_state_dict: the saved group has decoupled_weight_decay=False (torch.optim.Adam's L2 penalty, not AdamW)")
+        moments, t = {}, None
+        for i, entry in sd["state"].items():
+            if not isinstance(i, int) or not 0 <= i < len(self.params):
+                raise ValueError(f"AdamW.load_state_dict: state entry {i!r} names no parameter (this optimizer has {len(self.params)})")
+            for key in ("exp_avg", "exp_avg_sq"):
+                if tuple(entry[key].shape) != tuple(self.params[i].shape):
+                    raise ValueError(f"AdamW.load_state_dict: {key} of parameter {i} has shape {tuple(entry[key].shape)}, "
+                                     f"the parameter {tuple(self.params[i].shape)}")
+            step = float(entry["step"])                       # a tensor on any device, an int or a float
+            if step != int(step) or step < 0:
+                raise ValueError(f"AdamW.load_state_dict: step of parameter {i} is {step}")
+            if t is not None and int(step) != t:
+                raise ValueError(f"AdamW.load_state_dict: parameter {i} is at step {int(step)}, the parameters before it at step {t}; "
+                                 "this optimizer keeps one count for all of them")
+            t = int(step)
+            moments[i] = (entry["exp_avg"], entry["exp_avg_sq"])
+        return group, moments, t or 0, int(sd.get("cir", {}).get("skipped_steps", 0))
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict):
+        """Continue from `state_dict()`'s output or from a torch.optim.AdamW state dict (one group, no amsgrad / maximize).  Everything is
+        checked before anything changes (ValueError).  The moments are COPIED, as contiguous fp32 on their parameter's device: into the
+        views of the flat buffers where those exist, otherwise into per-tensor moments that the first flat step carries into its buffers
+        (step() above, one group per slab).  The hyperparameters come from the saved group, as in torch.  The applied / skipped counts go
+        into the device state; cir_adamw_begin recomputes both bias corrections from the count at every step, so nothing else is carried.
+        A parameter without an entry keeps no moments.  Call it with the parameters on the device they train on."""
+        group, moments, t, skipped = self._read_state_dict(sd)
+        flat_storages = {f.untyped_storage().data_ptr() for pair in self._flats.values() for f in pair}
+        for i, p in enumerate(self.params):
+            for store, k in ((self.m, 0), (self.v, 1)):
+                cur = store.get(id(p))
+                if i in moments:
+                    if cur is None:
+                        cur = store[id(p)] = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+                    cur.copy_(moments[i][k])
+                elif cur is not None:
+                    if cur.untyped_storage().data_ptr() in flat_storages:     # (a slice of a flat buffer cannot leave it: zero = no history)
+                        cur.zero_()
+                    else:
+                        del store[id(p)]
+        g = self.param_groups[0]
+        g["lr"], g["betas"], g["eps"], g["weight_decay"] = group["lr"], tuple(group["betas"]), group["eps"], group["weight_decay"]
+        self.betas, self.eps, self.wd = g["betas"], g["eps"], g["weight_decay"]          # (what step() reads)
+        if self._state is None:
+            dev = self.params[0].device if self.params else torch.device("cpu")
+            self._state = torch.zeros((8,), dtype=torch.int32, device=dev)
+        self._state[0:3] = torch.tensor([0, t, skipped], dtype=torch.int32)

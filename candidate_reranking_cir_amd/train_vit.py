@@ -22,7 +22,7 @@ import torch
 
 from . import lib as _lib
 from . import ops, train_ops as T
-from .train_core import _LN, Trainer, _cast, _install_grads, loss_scale
+from .train_core import _LN, Trainer, _cast, _install_grads, apply_pending_counters, loss_scale
 
 _P = "visual_encoder."
 
@@ -219,5 +219,6 @@ def vit_train(model, image: torch.Tensor) -> torch.Tensor:
     tr = getattr(model, "_vit_trainer", None)
     if tr is None or tr.dtype != vit_train_dtype(model):
         tr = model._vit_trainer = VitTrainer(model)
+        apply_pending_counters(model, "vit", tr)              # (seed, step_no) a checkpoint left for this trainer (load_training_state)
         tr.anchor = torch.zeros((1,), device=model.device, requires_grad=True)
     return _VitTrainFn.apply(tr.anchor, tr, image.to(model.device))
