@@ -382,33 +382,15 @@ extern "C" int cir_cross_attention_folded(const void* q, int64_t q_sb, int64_t q
                                           int64_t w_sb, const float* bv, const float* key_mask, int64_t mask_stride, void* out, int64_t o_st, int64_t o_sr,
                                           int64_t o_sb, int T, int L, int N, int D, int H, float scale, int dtype, void* stream) {
     using namespace cir;
-    CIR_CHECK_PTR(q); CIR_CHECK_PTR(x); CIR_CHECK_PTR(wkt); CIR_CHECK_PTR(wvp); CIR_CHECK_PTR(bv); CIR_CHECK_PTR(out);
-    if (T <= 0 || L <= 0 || N <= 0) return CIR_EINVAL;
-    if (D != kFoldD || H != 12 || L > 32 || N > 608) return CIR_ESHAPE;
-    if (dtype != CIR_BF16 && dtype != CIR_F16) return CIR_EDTYPE;
-    if (!cir_aligned16(q) || !cir_aligned16(x) || !cir_aligned16(wkt) || !cir_aligned16(wvp) || !cir_aligned16(bv) || (reinterpret_cast<uintptr_t>(out) & 7) ||
-        q_sb % 8 || q_rs % 8 || x_s1 % 8 || w_sb % 8 || o_st % 4 || o_sr % 4 || o_sb % 4)
-        return CIR_EALIGN;
-    if ((int64_t)T * 2 > 0x7fffffff) return CIR_ESHAPE;
     FoldArgs a;
-    a.q = q; a.q_sb = q_sb; a.q_rs = q_rs; a.x = x; a.x_s1 = x_s1; a.wkt = wkt; a.wvp = wvp; a.w_sb = w_sb; a.bv = bv;
-    a.out = out; a.o_st = o_st; a.o_sr = o_sr; a.o_sb = o_sb; a.T = T; a.L = L; a.N = N; a.scale = scale;
-    a.mask = key_mask; a.m_st = mask_stride;
-    if (key_mask && mask_stride < N) return CIR_ESHAPE;
+    const int rc = fold_args(a, q, q_sb, q_rs, x, x_s1, wkt, wvp, w_sb, bv, key_mask, mask_stride, out, o_st, o_sr, o_sb, T, L, N, D, H, scale, dtype,
+                             32, 608, (int64_t)T * 2);
+    if (rc != CIR_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (N > 16 * kFoldKB) return launch_fold16(a, dtype, s);       // 225 .. 608 keys: the 16-rows-per-wave kernel (xattn_fold16.hip)
-    const size_t lds = 2 * kFoldBuf + 32 * kStrideQ;
-    dim3 grid((unsigned)(8 * ((T + 3) / 4))), block(512);
-#define CIR_FOLD_LAUNCH(TT, MK)                                                                                                                   \
-    do {                                                                                                                                          \
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fold_kernel<TT, MK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return (int)e;                                                                                                       \
-        hipLaunchKernelGGL((xattn_fold_kernel<TT, MK>), grid, block, lds, s, a);                                                                  \
-    } while (0)
-    if (dtype == CIR_BF16) { if (key_mask) CIR_FOLD_LAUNCH(__bf16, true); else CIR_FOLD_LAUNCH(__bf16, false); }
-    else { if (key_mask) CIR_FOLD_LAUNCH(_Float16, true); else CIR_FOLD_LAUNCH(_Float16, false); }
-#undef CIR_FOLD_LAUNCH
-    CIR_LAUNCH_RESULT();
+    if (N > 16 * kFoldKB) return launch_fold16(a, dtype, s);       // 225 .. 608 keys: the 16-rows-per-wave kernel (xattn_fold_units.hip)
+    const FoldKernel k = dtype == CIR_BF16 ? (key_mask ? xattn_fold_kernel<__bf16, true> : xattn_fold_kernel<__bf16, false>)
+                                           : (key_mask ? xattn_fold_kernel<_Float16, true> : xattn_fold_kernel<_Float16, false>);
+    return fold_launch(k, dim3((unsigned)(8 * ((T + 3) / 4))), dim3(512), 2 * kFoldBuf + 32 * kStrideQ, s, a);
 }
 
 #if FOLD_DBG & 8

@@ -1,5 +1,5 @@
-// Shared pieces of the folded cross-attention kernels (xattn_fold.hip: N <= 224 keys, 48 query rows per wave; xattn_fold16.hip: N <= 608
-// keys, 16 query rows per wave).
+// Shared pieces of the folded cross-attention kernels (xattn_fold.hip: N <= 224 keys, 48 query rows per wave; xattn_fold_units.hip: N <= 608
+// keys or L <= 64 tokens, 16-row blocks).
 #pragma once
 #include "common.hpp"
 #include "gemm_args.hpp"
@@ -43,7 +43,37 @@ __device__ __forceinline__ typename Elem<T>::x8 pack_acc2(const f32x4& lo, const
 }
 
 
+// The checks common to the folded entry points, in the order that decides which code a bad call gets, then the FoldArgs fill.  The caller
+// names its limits (max_l tokens, max_n keys) and the workgroup count its grid must hold in 31 bits.
+inline int fold_args(FoldArgs& a, const void* q, int64_t q_sb, int64_t q_rs, const void* x, int64_t x_s1, const void* wkt, const void* wvp, int64_t w_sb,
+                     const float* bv, const float* key_mask, int64_t mask_stride, void* out, int64_t o_st, int64_t o_sr, int64_t o_sb, int T, int L, int N,
+                     int D, int H, float scale, int dtype, int max_l, int max_n, int64_t grid_bound) {
+    CIR_CHECK_PTR(q); CIR_CHECK_PTR(x); CIR_CHECK_PTR(wkt); CIR_CHECK_PTR(wvp); CIR_CHECK_PTR(bv); CIR_CHECK_PTR(out);
+    if (T <= 0 || L <= 0 || N <= 0) return CIR_EINVAL;
+    if (D != kFoldD || H != 12 || L > max_l || N > max_n) return CIR_ESHAPE;
+    if (dtype != CIR_BF16 && dtype != CIR_F16) return CIR_EDTYPE;
+    if (!cir_aligned16(q) || !cir_aligned16(x) || !cir_aligned16(wkt) || !cir_aligned16(wvp) || !cir_aligned16(bv) || (reinterpret_cast<uintptr_t>(out) & 7) ||
+        q_sb % 8 || q_rs % 8 || x_s1 % 8 || w_sb % 8 || o_st % 4 || o_sr % 4 || o_sb % 4)
+        return CIR_EALIGN;
+    if (grid_bound > 0x7fffffff) return CIR_ESHAPE;
+    if (key_mask && mask_stride < N) return CIR_ESHAPE;
+    a.q = q; a.q_sb = q_sb; a.q_rs = q_rs; a.x = x; a.x_s1 = x_s1; a.wkt = wkt; a.wvp = wvp; a.w_sb = w_sb; a.bv = bv;
+    a.out = out; a.o_st = o_st; a.o_sr = o_sr; a.o_sb = o_sb; a.T = T; a.L = L; a.N = N; a.scale = scale;
+    a.mask = key_mask; a.m_st = mask_stride;
+    return CIR_OK;
+}
+
+// Every folded kernel takes its FoldArgs by value and its X buffers and q stage as dynamic LDS above the 64-KiB default: raise the limit, launch
+using FoldKernel = void (*)(const FoldArgs);
+inline int fold_launch(FoldKernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const FoldArgs& a) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, a);
+    CIR_LAUNCH_RESULT();
+}
+
 // N <= 608 keys (the reference's 384-px geometry: 577 tokens): one 16-row block per wave, three workgroups per (candidate, branch)
+// (xattn_fold_units.hip)
 int launch_fold16(const FoldArgs& a, int dtype, hipStream_t s);
 
 }  // namespace cir

@@ -1,15 +1,21 @@
-// cir_cross_attention_folded_long: the query-side fold of xattn_fold.hip for captions of up to 64 tokens against up to 224 image tokens
-// (nlvr_encoder.py:150-168, 183-217 with encoder_hidden_states = the candidate's image tokens; the reference tokenises with
-// padding='longest' and no 32-token cut, blip_stage2.py:113, and FashionIQ joins two captions per query).  The work is 12 ceil(L / 16)
-// 16-row blocks per (candidate, branch) and nothing more: a wave owns ONE head and NB consecutive 16-token blocks of it, which share every
-// X fragment read from LDS and every W_k^T / W_v fragment of their head:
-//     L <= 16: NB = 1, one wave per head      L <= 32: NB = 2, one wave per head      L <= 48: NB = 3, one wave per head (S^T = 168 registers)
-//     L <= 64: NB = 2, two waves per head (S^T = 112 registers)
-// A workgroup covers 4 heads (4 or 8 waves); three workgroups per (candidate, branch), none waits for another.  Same four products and
-// the same accumulator-as-operand chaining as xattn_fold.hip (G1 Q'^T = W_k^T q^T, G2 S^T += X Q'^T, softmax in registers, G3 C'^T = X^T P^T,
-// G4 ctx^T += W_v C'^T, epilogue ctx / rowsum + b_v), the same packed weights (ops.fold_pack_key / fold_pack_value) and X staged per 32-feature
-// UNIT in xattn_fold16.hip's two LDS layouts (64-byte rows, chunk position XOR-swizzled by {0, 2, 3, 1}[(row >> 2) & 3], for phase 1's
-// ds_read_b128; 96-byte rows for phase 2's transposing reads).
+// The query-side fold of xattn_fold.hip in 16-row steps: one kernel body, X staged per 32-feature UNIT, behind two entry points -
+//   cir_cross_attention_folded for 225 .. 608 image tokens (the reference's 384-px geometry: 577 tokens; validate_stage2.py:327), L <= 32;
+//   cir_cross_attention_folded_long for captions of up to 64 tokens against up to 224 image tokens (nlvr_encoder.py:150-168, 183-217 with
+//   encoder_hidden_states = the candidate's image tokens; the reference tokenises with padding='longest' and no 32-token cut,
+//   blip_stage2.py:113, and FashionIQ joins two captions per query).
+// The work is 12 ceil(L / 16) 16-row blocks per (candidate, branch) and nothing more: a wave owns ONE head and NB consecutive 16-token blocks of
+// it, which share every X fragment read from LDS and every W_k^T / W_v fragment of their head.  The transposed score tile S^T of a block
+// against KB 16-key blocks is KB accumulator tiles = 4 KB registers, and that decides the instantiations:
+//     608 keys (KB = 38), L <= 32: NB = 1, two waves per head (S^T = 152 registers; three blocks, as in the 224-key kernel, would need 456)
+//     224 keys (KB = 14), L <= 16: NB = 1, one wave per head      L <= 32: NB = 2, one wave per head
+//                         L <= 48: NB = 3, one wave per head (S^T = 168 registers)      L <= 64: NB = 2, two waves per head (S^T = 112 registers)
+// A workgroup covers 4 heads (4 or 8 waves); three workgroups per (candidate, branch), none waits for another: 4 heads x 32 tokens = 128 stacked
+// query rows are what 8 waves of one block each hold.  Same four products and the same accumulator-as-operand chaining as xattn_fold.hip
+// (G1 Q'^T = W_k^T q^T, G2 S^T += X Q'^T, softmax in registers, G3 C'^T = X^T P^T, G4 ctx^T += W_v C'^T, epilogue ctx / rowsum + b_v) and the same
+// packed weights (ops.fold_pack_key / fold_pack_value).  X is staged per UNIT (KB x 16 keys x 32 features, two buffers) in two LDS layouts:
+// 64-byte rows with the chunk position XOR-swizzled by f(row) = {0, 2, 3, 1}[(row >> 2) & 3] for phase 1's ds_read_b128 (the four 16-lane
+// groups of a b128 read then hit 64 distinct banks), 96-byte rows for phase 2's transposing reads (8 rows x 8 dwords at a 24-dword stride:
+// distinct multiples of 8).  At 577 keys, per (candidate, branch): 1.50 GFLOP instead of 2.83 (K|V GEMM 2.72 + attention 0.11).
 // A query row is one COLUMN of every product, so its result depends on nothing but its own q row, X and the weights: every instantiation
 // runs the same accumulation order per row (units in order, key blocks in order), hence a row's bits do not depend on T, on the candidate's
 // place in the batch, on L or on the block assignment.  Rows >= L are computed on zero queries and never stored; keys >= N are read
@@ -19,18 +25,29 @@
 
 namespace cir {
 
-constexpr int kBufL = 1536 * 16;             // one X-unit buffer: phase 2 stages 1536 slots of 16 B (224 rows x 6 slots = 1344), phase 1 1024 (224 x 4 = 896)
-constexpr int kStrideQL = 544;               // q rows in LDS: 4 heads x 64 x 2 B + 32 (136 dwords = 8 mod 64: conflict-free b128 fragment reads)
-constexpr int kStrideP2L = 96;               // phase 2's row stride
+constexpr int kStrideQU = 544;               // q rows in LDS: 4 heads x 64 x 2 B + 32 (136 dwords = 8 mod 64: conflict-free b128 fragment reads)
+constexpr int kStrideP2U = 96;               // phase 2's row stride
 
-// NB 16-row blocks per wave, WPH waves per head: rows 16 (NB (wave % WPH) + nb) + l16 of head 4 hg + wave / WPH
-template <typename T, bool MASKED, int NB, int WPH>
-__device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
+// What follows from the key-block count: KB 16-key blocks over 4 WPH waves, 1-KiB DMA pieces (64 slots of 16 B) per wave and unit
+template <int NB, int WPH, int KB>
+struct FoldUnitGeom {
+    static constexpr int kWaves = 4 * WPH;
+    static constexpr int kRows = 16 * NB * WPH;                              // token rows the workgroup covers
+    static constexpr int kP1 = (KB + kWaves - 1) / kWaves;                   // phase 1: 16 KB rows x 4 slots = KB pieces
+    static constexpr int kP2 = (3 * KB + 2 * kWaves - 1) / (2 * kWaves);     // phase 2: 16 KB rows x 6 slots = 1.5 KB pieces
+    static constexpr int kBuf = kWaves * kP2 * 1024;                         // one X-unit buffer (608 keys: 64 KiB, 224 keys: 24 KiB)
+    static constexpr int kLds = 2 * kBuf + kRows * kStrideQU;
+};
+
+// NB 16-row blocks per wave, WPH waves per head, KB 16-key blocks: rows 16 (NB (wave % WPH) + nb) + l16 of head 4 hg + wave / WPH
+template <typename T, bool MASKED, int NB, int WPH, int KB>
+__device__ __forceinline__ void fold_unit_body(const FoldArgs& a) {
     using X8 = typename Elem<T>::x8;
+    using G = FoldUnitGeom<NB, WPH, KB>;
+    static_assert(KB <= 38 && KB % 2 == 0, "phase 2's steps are written out for at most 38 key blocks, and P packs them in pairs");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int kThreads = 256 * WPH;
-    constexpr int kRows = 16 * NB * WPH;                         // token rows this instantiation covers
-    constexpr int kP1 = 4 / WPH, kP2 = 6 / WPH;                  // DMA pieces per wave and unit: 1024 / 1536 slots over 4 WPH waves
+    constexpr int kThreads = 64 * G::kWaves;
+    constexpr int kRows = G::kRows, kP1 = G::kP1, kP2 = G::kP2, kBuf = G::kBuf;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -48,7 +65,7 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
     const int tok0 = 16 * NB * (wave % WPH) + l16;               // this lane's token row in block nb: tok0 + 16 nb
 
     // q of this workgroup's 4 heads in LDS: kRows token rows x 256 values, rows beyond L zero
-    char* const qs = smem + 2 * kBufL;
+    char* const qs = smem + 2 * kBuf;
     {
         const T* qb_ = reinterpret_cast<const T*>(a.q) + (int64_t)b * a.q_sb + (int64_t)t * a.L * a.q_rs + hg * 256;
 #pragma unroll
@@ -59,10 +76,10 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = static_cast<T>(0.f);
             if (row < a.L) v = *reinterpret_cast<const X8*>(qb_ + (int64_t)row * a.q_rs + ch * 8);
-            *reinterpret_cast<X8*>(qs + row * kStrideQL + ch * 16) = v;
+            *reinterpret_cast<X8*>(qs + row * kStrideQU + ch * 16) = v;
         }
     }
-    const int qoff = tok0 * kStrideQL + (hw * 64 + 8 * g) * 2;   // block nb: + 16 nb rows
+    const int qoff = tok0 * kStrideQU + (hw * 64 + 8 * g) * 2;   // block nb: + 16 nb rows
 
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, a.N * kFoldD * 2, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(reinterpret_cast<const T*>(a.wkt) + (int64_t)b * a.w_sb), 0, kFoldD * kFoldD * 2, 0x00020000);
@@ -75,14 +92,14 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
     for (int j = 0; j < kP1; ++j) {
         const int s = (wave * kP1 + j) * 64 + lane;
         const int row = s >> 2;
-        const int f = (0x1E >> (2 * ((row >> 2) & 3))) & 3;      // {0, 2, 3, 1}[(row >> 2) & 3]
+        const int f = (0x1E >> (2 * ((row >> 2) & 3))) & 3;      // {0, 2, 3, 1}[(row >> 2) & 3] packed two bits each: 0b00_01_11_10 -> 0x1E
         xoff1[j] = (min(row, a.N - 1) * kFoldD + (((s & 3) ^ f) * 8)) * 2;
     }
 
-    // ---------------------------------------------------------------- phase 1: S^T (224 keys x 16 NB rows per wave) ----------------------
-    f32x4 S[kFoldKB][NB];
+    // ---------------------------------------------------------------- phase 1: S^T (16 KB keys x 16 NB rows per wave) --------------------
+    f32x4 S[KB][NB];
 #pragma unroll
-    for (int kb = 0; kb < kFoldKB; ++kb)
+    for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) S[kb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     X8 w[2][2];                                                   // [interleaved 16-feature tile][k-step]
@@ -99,7 +116,7 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
     for (int u = 0; u < 24; ++u) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        const char* xs = smem + (u & 1) * kBufL;
+        const char* xs = smem + (u & 1) * kBuf;
         // G1: Q'^T tiles of features [32 u, 32 u + 32), interleaved (tile fbh row 4 g' + r = feature 8 g' + 4 fbh + r), for the NB row blocks
         f32x4 a1[2][NB];
 #pragma unroll
@@ -110,7 +127,7 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
         for (int ks = 0; ks < 2; ++ks) {
             X8 qf[NB];
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) qf[nb] = *reinterpret_cast<const X8*>(qs + qoff + nb * 16 * kStrideQL + 64 * ks);
+            for (int nb = 0; nb < NB; ++nb) qf[nb] = *reinterpret_cast<const X8*>(qs + qoff + nb * 16 * kStrideQU + 64 * ks);
 #pragma unroll
             for (int fbh = 0; fbh < 2; ++fbh)
 #pragma unroll
@@ -124,7 +141,7 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
         auto mem_op = [&](int j) {                                // next unit's 4 weight fragments, then its DMA pieces: one request per key block
             if (!more) return;
             if (j < 4) w[j >> 1][j & 1] = wload<X8>(rs_k, wlane, ((((u + 1) * 2 + (j >> 1)) * 12 + head) * 2 + (j & 1)) * 1024);
-            else if (j < 4 + kP1) FOLD_DMA(rs_x, xoff1[j - 4], (u + 1) * 64, smem + ((u + 1) & 1) * kBufL + (wave * kP1 + j - 4) * 1024);
+            else if (j < 4 + kP1) FOLD_DMA(rs_x, xoff1[j - 4], (u + 1) * 64, smem + ((u + 1) & 1) * kBuf + (wave * kP1 + j - 4) * 1024);
         };
         // G2: k-slot (g, j) = feature 32 u + 8 g + j: piece g of the key's 64-byte row, at position g ^ f(row)
         const char* xr = xs + l16 * 64 + ((g ^ fr) << 4);
@@ -134,8 +151,8 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
 #pragma unroll
         for (int kb = 0; kb < kAhead; ++kb) xa[kb] = rd(kb);
 #pragma unroll
-        for (int kb = 0; kb < kFoldKB; ++kb) {
-            if (kb + kAhead < kFoldKB) xa[(kb + kAhead) % (kAhead + 1)] = rd(kb + kAhead);
+        for (int kb = 0; kb < KB; ++kb) {
+            if (kb + kAhead < KB) xa[(kb + kAhead) % (kAhead + 1)] = rd(kb + kAhead);
             mem_op(kb);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -151,13 +168,13 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
     // ---------------------------------------------------------------- softmax over the keys of each row (log2 domain) -------------------
     const float sl = a.scale * 1.4426950408889634f;
     float rinv[NB];
-    X8 P[kFoldKB / 2][NB];
+    X8 P[KB / 2][NB];
     // logits and row maxima: the key's validity (a compare = an SGPR pair) and its mask value serve the NB blocks at once and die
     float mx[NB];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) mx[nb] = -INFINITY;
 #pragma unroll
-    for (int kb = 0; kb < kFoldKB; ++kb)
+    for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int key = 16 * kb + 4 * gb + r;
@@ -172,7 +189,7 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
                 S[kb][nb][r] = v;
                 mx[nb] = fmaxf(mx[nb], v);
             }
-            if (r == 3) __builtin_amdgcn_sched_barrier(0);       // (keeps the compares next to their selects: 56 hoisted compare masks do not fit the SGPR file)
+            if (r == 3) __builtin_amdgcn_sched_barrier(0);       // (keeps the compares next to their selects: 4 KB hoisted compare masks do not fit the SGPR file)
         }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -182,7 +199,7 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
         const float ms = MASKED ? m : m * sl;
         float sum = 0.f;
 #pragma unroll
-        for (int kb = 0; kb < kFoldKB; ++kb)
+        for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float p = MASKED ? __builtin_amdgcn_exp2f(S[kb][nb][r] - ms) : __builtin_amdgcn_exp2f(fmaf(S[kb][nb][r], sl, -ms));
@@ -193,7 +210,7 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
         sum += __shfl_xor(sum, 32, 64);
         rinv[nb] = 1.0f / sum;
 #pragma unroll
-        for (int p = 0; p < kFoldKB / 2; ++p) P[p][nb] = pack_acc2<T>(S[2 * p][nb], S[2 * p + 1][nb]);
+        for (int p = 0; p < KB / 2; ++p) P[p][nb] = pack_acc2<T>(S[2 * p][nb], S[2 * p + 1][nb]);
     }
 
     // ---------------------------------------------------------------- phase 2: ctx^T (64 d x 16 NB rows per wave) ------------------------
@@ -218,16 +235,16 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
 #pragma unroll
         for (int j = 0; j < kP2; ++j) FOLD_DMA(rs_x, xoff2[j], 0, base + j * 1024);
     }
-    const int troff = (4 * gb + (l16b >> 2)) * kStrideP2L + (4 * (l16b & 3)) * 2;
+    const int troff = (4 * gb + (l16b >> 2)) * kStrideP2U + (4 * (l16b & 3)) * 2;
     for (int u = 0; u < 24; ++u) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         const bool more = u + 1 < 24;
         auto mem_op = [&](int j) {                                // this unit's 4 W_v fragments (needed by G4 at its end), then the next unit's DMA pieces
             if (j < 4) wv[j] = wload<X8>(rs_v, wlane2, ((u * 4 + j) * 12 + head) * 1024);
-            else if (j < 4 + kP2 && more) FOLD_DMA(rs_x, xoff2[j - 4], (u + 1) * 64, smem + ((u + 1) & 1) * kBufL + (wave * kP2 + j - 4) * 1024);
+            else if (j < 4 + kP2 && more) FOLD_DMA(rs_x, xoff2[j - 4], (u + 1) * 64, smem + ((u + 1) & 1) * kBuf + (wave * kP2 + j - 4) * 1024);
         };
-        const unsigned xaddr = (unsigned)(size_t)(lptr_t)(smem + (u & 1) * kBufL + troff);
+        const unsigned xaddr = (unsigned)(size_t)(lptr_t)(smem + (u & 1) * kBuf + troff);
         f32x4 a3[2][NB];
 #pragma unroll
         for (int fbh = 0; fbh < 2; ++fbh)
@@ -235,19 +252,21 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
             for (int nb = 0; nb < NB; ++nb) a3[fbh][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
         u32x2 lo[3], hi[3];
         // The transposing reads are inline asm with counted waits of their own (see xattn_fold.hip); step I = key pair I >> 1 (32 keys),
-        // 16-feature block I & 1.  Expanded by macro: the asm immediates need the step index as a literal.
-#define FOLDL_TR(SLOT, I)                                                                                                       \
+        // 16-feature block I & 1.  Expanded by macro, not by `#pragma unroll`: the asm immediates need the step index as a literal, and with a
+        // 38-case switch inside the loop hipcc gave up unrolling - P and the fragment registers then lived in scratch.  38 steps are written
+        // out; `if constexpr` discards those at and beyond KB.
+#define FOLDU_TR(SLOT, I)                                                                                                       \
         asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"                                 \
-                     : "=&v"(lo[SLOT]), "=&v"(hi[SLOT]) : "v"(xaddr), "n"((32 * ((I) >> 1)) * kStrideP2L + (16 * ((I) & 1)) * 2),    \
-                       "n"((32 * ((I) >> 1) + 16) * kStrideP2L + (16 * ((I) & 1)) * 2) : "memory")
-        FOLDL_TR(0, 0);
-        FOLDL_TR(1, 1);
-#define FOLDL_STEP(I)                                                                                                             \
-        {                                                                                                                          \
-            if ((I) + 2 < kFoldKB) FOLDL_TR(((I) + 2) % 3, (I) + 2 < kFoldKB ? (I) + 2 : 0);                                        \
+                     : "=&v"(lo[SLOT]), "=&v"(hi[SLOT]) : "v"(xaddr), "n"((32 * ((I) >> 1)) * kStrideP2U + (16 * ((I) & 1)) * 2),    \
+                       "n"((32 * ((I) >> 1) + 16) * kStrideP2U + (16 * ((I) & 1)) * 2) : "memory")
+        FOLDU_TR(0, 0);
+        FOLDU_TR(1, 1);
+#define FOLDU_STEP(I)                                                                                                             \
+        if constexpr ((I) < KB) {                                                                                                  \
+            if constexpr ((I) + 2 < KB) FOLDU_TR(((I) + 2) % 3, (I) + 2);                                                           \
             mem_op(I);                                                                                                             \
-            if ((I) + 2 < kFoldKB) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(lo[(I) % 3]), "+v"(hi[(I) % 3]));                     \
-            else if ((I) + 1 < kFoldKB) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(lo[(I) % 3]), "+v"(hi[(I) % 3]));                \
+            if constexpr ((I) + 2 < KB) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(lo[(I) % 3]), "+v"(hi[(I) % 3]));                \
+            else if constexpr ((I) + 1 < KB) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(lo[(I) % 3]), "+v"(hi[(I) % 3]));           \
             else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(lo[(I) % 3]), "+v"(hi[(I) % 3]));                                       \
             __builtin_amdgcn_sched_barrier(0);                                                                                     \
             const u32x4 both = {lo[(I) % 3].x, lo[(I) % 3].y, hi[(I) % 3].x, hi[(I) % 3].y};                                        \
@@ -255,10 +274,12 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
             _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) a3[(I) & 1][nb] = Elem<T>::mfma16(xa, P[(I) >> 1][nb], a3[(I) & 1][nb]); \
             __builtin_amdgcn_sched_barrier(0);                                                                                     \
         }
-        FOLDL_STEP(0) FOLDL_STEP(1) FOLDL_STEP(2) FOLDL_STEP(3) FOLDL_STEP(4) FOLDL_STEP(5) FOLDL_STEP(6)
-        FOLDL_STEP(7) FOLDL_STEP(8) FOLDL_STEP(9) FOLDL_STEP(10) FOLDL_STEP(11) FOLDL_STEP(12) FOLDL_STEP(13)
-#undef FOLDL_STEP
-#undef FOLDL_TR
+#define FOLDU_STEP4(I) FOLDU_STEP(I) FOLDU_STEP((I) + 1) FOLDU_STEP((I) + 2) FOLDU_STEP((I) + 3)
+        FOLDU_STEP4(0) FOLDU_STEP4(4) FOLDU_STEP4(8) FOLDU_STEP4(12) FOLDU_STEP4(16) FOLDU_STEP4(20) FOLDU_STEP4(24) FOLDU_STEP4(28) FOLDU_STEP4(32)
+        FOLDU_STEP(36) FOLDU_STEP(37)
+#undef FOLDU_STEP4
+#undef FOLDU_STEP
+#undef FOLDU_TR
         // G4: ctx^T += W_v[:, these 32 features (k-slot order)] C'^T
         X8 bq[NB];
 #pragma unroll
@@ -289,37 +310,36 @@ __device__ __forceinline__ void fold_long_body(const FoldArgs& a) {
     }
 }
 
-// one wave per head, NB blocks each (4 waves); two waves per head, two blocks each (8 waves).  Two waves per SIMD either way: 256 registers
-// (two kernels around one body: a launch bound that depends on a template parameter, 256 * WPH, fails to substitute in hipcc's host pass)
-template <typename T, bool MASKED, int NB>
-__global__ __launch_bounds__(256, 2) void xattn_fold_long_kernel(const FoldArgs a) { fold_long_body<T, MASKED, NB, 1>(a); }
+// Three kernels around the one body, two waves per SIMD each (256 registers): 608 keys, two waves of one block per head (8 waves); 224 keys,
+// one wave of NB blocks per head (4 waves); 224 keys, two waves of two blocks per head (8 waves).
+// (separate kernels with literal bounds: a launch bound that depends on a template parameter, 256 * WPH, fails to substitute in hipcc's host pass)
 template <typename T, bool MASKED>
-__global__ __launch_bounds__(512, 2) void xattn_fold_long64_kernel(const FoldArgs a) { fold_long_body<T, MASKED, 2, 2>(a); }
+__global__ __launch_bounds__(512, 2) void xattn_fold16_kernel(const FoldArgs a) { fold_unit_body<T, MASKED, 1, 2, 38>(a); }
+template <typename T, bool MASKED, int NB>
+__global__ __launch_bounds__(256, 2) void xattn_fold_long_kernel(const FoldArgs a) { fold_unit_body<T, MASKED, NB, 1, kFoldKB>(a); }
+template <typename T, bool MASKED>
+__global__ __launch_bounds__(512, 2) void xattn_fold_long64_kernel(const FoldArgs a) { fold_unit_body<T, MASKED, 2, 2, kFoldKB>(a); }
 
-template <typename T, bool MASKED, int NB, int WPH>
-static int launch_fold_long(const FoldArgs& a, hipStream_t s) {
-    const size_t lds = 2 * kBufL + 16 * NB * WPH * kStrideQL;
+template <int NB, int WPH, int KB>
+static int launch_fold_units(FoldKernel kernel, const FoldArgs& a, hipStream_t s) {
+    using G = FoldUnitGeom<NB, WPH, KB>;
     const int64_t per_branch = 3 * (int64_t)a.T;
-    dim3 grid((unsigned)(8 * ((per_branch + 3) / 4))), block(256 * WPH);
-    if constexpr (WPH == 2) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fold_long64_kernel<T, MASKED>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((xattn_fold_long64_kernel<T, MASKED>), grid, block, lds, s, a);
-    } else {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&xattn_fold_long_kernel<T, MASKED, NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((xattn_fold_long_kernel<T, MASKED, NB>), grid, block, lds, s, a);
-    }
-    return CIR_OK;
+    return fold_launch(kernel, dim3((unsigned)(8 * ((per_branch + 3) / 4))), dim3(64 * G::kWaves), G::kLds, s, a);
+}
+
+int launch_fold16(const FoldArgs& a, int dtype, hipStream_t s) {
+    const FoldKernel k = dtype == CIR_BF16 ? (a.mask ? xattn_fold16_kernel<__bf16, true> : xattn_fold16_kernel<__bf16, false>)
+                                           : (a.mask ? xattn_fold16_kernel<_Float16, true> : xattn_fold16_kernel<_Float16, false>);
+    return launch_fold_units<1, 2, 38>(k, a, s);
 }
 
 // cost in 16-row steps: 1, 2 or 3 blocks per wave and head up to 48 tokens, two waves of 2 blocks per head above
 template <typename T, bool MASKED>
-static int launch_fold_long_l(const FoldArgs& a, hipStream_t s) {
-    if (a.L <= 16) return launch_fold_long<T, MASKED, 1, 1>(a, s);
-    if (a.L <= 32) return launch_fold_long<T, MASKED, 2, 1>(a, s);
-    if (a.L <= 48) return launch_fold_long<T, MASKED, 3, 1>(a, s);
-    return launch_fold_long<T, MASKED, 2, 2>(a, s);
+static int launch_fold_long(const FoldArgs& a, hipStream_t s) {
+    if (a.L <= 16) return launch_fold_units<1, 1, kFoldKB>(xattn_fold_long_kernel<T, MASKED, 1>, a, s);
+    if (a.L <= 32) return launch_fold_units<2, 1, kFoldKB>(xattn_fold_long_kernel<T, MASKED, 2>, a, s);
+    if (a.L <= 48) return launch_fold_units<3, 1, kFoldKB>(xattn_fold_long_kernel<T, MASKED, 3>, a, s);
+    return launch_fold_units<2, 2, kFoldKB>(xattn_fold_long64_kernel<T, MASKED>, a, s);
 }
 
 }  // namespace cir
@@ -330,23 +350,11 @@ extern "C" int cir_cross_attention_folded_long(const void* q, int64_t q_sb, int6
                                                int64_t w_sb, const float* bv, const float* key_mask, int64_t mask_stride, void* out, int64_t o_st,
                                                int64_t o_sr, int64_t o_sb, int T, int L, int N, int D, int H, float scale, int dtype, void* stream) {
     using namespace cir;
-    CIR_CHECK_PTR(q); CIR_CHECK_PTR(x); CIR_CHECK_PTR(wkt); CIR_CHECK_PTR(wvp); CIR_CHECK_PTR(bv); CIR_CHECK_PTR(out);
-    if (T <= 0 || L <= 0 || N <= 0) return CIR_EINVAL;
-    if (D != kFoldD || H != 12 || L > 64 || N > 16 * kFoldKB) return CIR_ESHAPE;
-    if (dtype != CIR_BF16 && dtype != CIR_F16) return CIR_EDTYPE;
-    if (!cir_aligned16(q) || !cir_aligned16(x) || !cir_aligned16(wkt) || !cir_aligned16(wvp) || !cir_aligned16(bv) || (reinterpret_cast<uintptr_t>(out) & 7) ||
-        q_sb % 8 || q_rs % 8 || x_s1 % 8 || w_sb % 8 || o_st % 4 || o_sr % 4 || o_sb % 4)
-        return CIR_EALIGN;
-    if ((int64_t)T * 6 + 8 > 0x7fffffff) return CIR_ESHAPE;
-    if (key_mask && mask_stride < N) return CIR_ESHAPE;
     FoldArgs a;
-    a.q = q; a.q_sb = q_sb; a.q_rs = q_rs; a.x = x; a.x_s1 = x_s1; a.wkt = wkt; a.wvp = wvp; a.w_sb = w_sb; a.bv = bv;
-    a.out = out; a.o_st = o_st; a.o_sr = o_sr; a.o_sb = o_sb; a.T = T; a.L = L; a.N = N; a.scale = scale;
-    a.mask = key_mask; a.m_st = mask_stride;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int rc;
-    if (dtype == CIR_BF16) rc = key_mask ? launch_fold_long_l<__bf16, true>(a, s) : launch_fold_long_l<__bf16, false>(a, s);
-    else rc = key_mask ? launch_fold_long_l<_Float16, true>(a, s) : launch_fold_long_l<_Float16, false>(a, s);
+    const int rc = fold_args(a, q, q_sb, q_rs, x, x_s1, wkt, wvp, w_sb, bv, key_mask, mask_stride, out, o_st, o_sr, o_sb, T, L, N, D, H, scale, dtype,
+                             64, 16 * kFoldKB, (int64_t)T * 6 + 8);
     if (rc != CIR_OK) return rc;
-    CIR_LAUNCH_RESULT();
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == CIR_BF16) return key_mask ? launch_fold_long<__bf16, true>(a, s) : launch_fold_long<__bf16, false>(a, s);
+    return key_mask ? launch_fold_long<_Float16, true>(a, s) : launch_fold_long<_Float16, false>(a, s);
 }

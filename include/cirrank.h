@@ -233,7 +233,7 @@ int cir_cls_cross_attention(const void* x, int64_t x_s1, const int64_t* x_index,
  * (u < D / 32 feature units, t < 2, s < 2, e < 4, h < 12; candidate_reranking_cir_amd/ops.py: fold_pack_key / fold_pack_value);
  * bv (2, D) fp32 value bias; out (T, L, 2, D)-shaped through strides.
  * D = 768, H = 12, L <= 32, N <= 608 (N <= 224: 48 query rows per wave, csrc/xattn_fold.hip; 225 .. 608 - the 384-px geometry's 577 tokens -: 16 rows per
- * wave, csrc/xattn_fold16.hip) (CIR_ESHAPE otherwise: use cir_gemm_bias_act + cir_attention).  key_mask (ABI v14; NULL = none): additive fp32
+ * wave, csrc/xattn_fold_units.hip) (CIR_ESHAPE otherwise: use cir_gemm_bias_act + cir_attention).  key_mask (ABI v14; NULL = none): additive fp32
  * mask (T, N), rows mask_stride apart, shared by both branches - the (1 - attention_mask) * finfo.min of padded candidate token sets
  * (nlvr_encoder.py:863-868): logits = scores * scale + mask; masks below -2e38 are clamped there (all-masked rows stay uniform).  16-bit operands, fp32
  * accumulation and softmax; Q' = q W_k and C' = P X are rounded to the operand type where the projected path rounds K and V.
@@ -244,7 +244,7 @@ int cir_cross_attention_folded(const void* q, int64_t q_sb, int64_t q_rs, const 
                                int T, int L, int N, int D, int H, float scale, int dtype, void* stream);
 
 /*
- * cir_cross_attention_folded for captions of up to 64 tokens (csrc/xattn_fold_long.hip; additive within ABI v15): the same operator
+ * cir_cross_attention_folded for captions of up to 64 tokens (csrc/xattn_fold_units.hip; additive within ABI v15): the same operator
  * (nlvr_encoder.py:150-168, 183-217), the same operands, packed weights, key mask and strides, for the captions the reference does not cut at 32
  * tokens (blip_stage2.py:113: padding='longest', no max_length; FashionIQ joins two captions per query).  D = 768, H = 12, L <= 64, N <= 224
  * (CIR_ESHAPE otherwise: use cir_gemm_bias_act + cir_attention).  A wave owns one head and up to three 16-token blocks of it; the cost grows in

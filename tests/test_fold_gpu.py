@@ -36,7 +36,7 @@ def _reference(q, x, wk, bk, wv, bv, l):
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
-@pytest.mark.parametrize("t_n,l,n", [(3, 32, 197), (5, 11, 197), (2, 32, 224), (4, 1, 50), (2, 17, 17), (2, 32, 577), (3, 9, 300), (1, 32, 608), (5, 30, 225)])
+@pytest.mark.parametrize("t_n,l,n", [(3, 32, 197), (5, 11, 197), (2, 32, 224), (4, 1, 50), (2, 17, 17), (2, 32, 577), (3, 9, 300), (1, 32, 608), (5, 30, 225), (2, 1, 608)])
 def test_folded_cross_attention_against_fp64_and_projected_path(ops, dtype, t_n, l, n):
     q = _rand((2, t_n * l, D), 1.0, 1, dtype)
     x = _rand((t_n, n, D), 1.0, 2, dtype)
@@ -154,6 +154,38 @@ def test_folded_cross_attention_with_a_key_mask(ops, t_n, l, n):
     allm = torch.empty_like(out)
     ops.cross_attention_folded(*args, allm, l, 0.125, mask=torch.full((t_n, n), torch.finfo(torch.float32).min, device="cuda"))
     assert bool(torch.isfinite(allm.float()).all())
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+def test_fold16_rows_do_not_depend_on_their_launch(ops, dtype):
+    """The 16-rows-per-wave kernel for 225 .. 608 keys, at the smallest key count that reaches it: (a) a candidate's rows are the same in a
+    batch of 7 and alone, (b) the first 17 token rows are the same whether the caption has 17 or 32 tokens, (c) a launch repeats itself,
+    (d) an all-zero key mask stays next to the unmasked launch (the masked form scales the scores before the maximum: one rounding apart,
+    so not bit for bit).  The bound of (d) is ONE ULP OF THE OUTPUT below |ctx| = 4: the logits differ in their last fp32 bit, the fp32
+    context by ~1e-6, and a 16-bit store then lands on the neighbouring value or on the same one.  For fp16 that is the 2e-3 this file holds
+    for the other folded kernels (2^-9 = 1.95e-3); bf16 keeps eight mantissa bits fewer, 2^-6 = 1.56e-2.  (Measured at |ctx| < 2, one ulp
+    each: fp16 9.77e-4 = 2^-10, bf16 3.91e-3 = 2^-8.)"""
+    n, t7 = 225, 7
+    wk, wv, bv = _rand((2, D, D), 0.03, 33, dtype), _rand((2, D, D), 0.03, 34, dtype), _rand((2, D), 0.5, 36, torch.float32)
+    x = _rand((t7, n, D), 1.0, 32, dtype)
+    q32 = _rand((2, t7, 32, D), 1.0, 31, dtype)                           # (branch, candidate, token, D)
+    wkp, wvp, bvc = ops.fold_pack_key(wk).cuda(), ops.fold_pack_value(wv).cuda(), bv.cuda()
+
+    def run(cands, l, mask=None):
+        q = q32[:, cands, :l].reshape(2, len(cands) * l, D).contiguous()      # the same q rows in this launch's (2, T L, D) layout
+        out = torch.empty((len(cands), l, 2, D), dtype=dtype, device="cuda")
+        ops.cross_attention_folded(q.cuda(), x[cands].cuda(), wkp, wvp, bvc, out, l, 0.125, mask=mask)
+        return out
+
+    every = list(range(t7))
+    batch = run(every, 32)
+    assert torch.equal(batch, run(every, 32))                               # (c)
+    assert torch.equal(batch[3], run([3], 32)[0])                           # (a)
+    assert torch.equal(run([0, 1], 17), batch[:2, :17])                     # (b)
+    zero = run(every, 32, mask=torch.zeros((t7, n), device="cuda"))         # (d)
+    apart = (batch.float() - zero.float()).abs().max().item()
+    print(f"\n[fold16 rows, {dtype}] zero mask vs unmasked: max|d| {apart:.2e} (|ctx| max {batch.float().abs().max().item():.2f})")
+    assert batch.float().abs().max().item() < 4.0 and apart < (2e-3 if dtype == torch.float16 else 1.6e-2)
 
 
 def test_engine_takes_the_fold_with_a_candidate_mask_and_counts_long_captions(ops):

@@ -1,4 +1,4 @@
-"""cir_cross_attention_folded_long: the query-side fold for captions of up to 64 tokens against up to 224 keys (csrc/xattn_fold_long.hip) -
+"""cir_cross_attention_folded_long: the query-side fold for captions of up to 64 tokens against up to 224 keys (csrc/xattn_fold_units.hip) -
 against the fp64 restatement of the reference's arithmetic and the projected path of this library on the inputs of tests/test_fold_gpu.py
 (q and x at sigma 1, weights at sigma 0.03, biases at sigma 0.5), with the bounds that file holds for the 32-token kernels: a row's error
 does not depend on how many rows share its launch.  Then the properties a longer caption adds: the token-to-block and head-to-wave maps of

@@ -4,7 +4,7 @@
 
 Every shipped precision mode is held to it: the exact mode to 5e-5 and the reference's sorted order (this pins the fp32 GEMM and
 `attn_f32_kernel` at 577 tokens against the reference, not only against fp64 torch); the 16-bit modes and text32 to floors measured on
-MI355X; the 577-token form of the query-side cross-attention fold (xattn_fold16.hip) on and off."""
+MI355X; the 577-token form of the query-side cross-attention fold (xattn_fold_units.hip) on and off."""
 import numpy as np
 import pytest
 import torch
@@ -88,7 +88,7 @@ def test_rank384_against_the_reference(fx, mode):
 
 
 def test_rank384_fold16_on_and_off(fx):
-    """577 keys run the 16-rows-per-wave form of the query-side fold (xattn_fold16.hip); with the fold off the K|V projection + attention
+    """577 keys run the 16-rows-per-wave form of the query-side fold (xattn_fold_units.hip); with the fold off the K|V projection + attention
     path computes the same cross-attention: both meet the reference, and they agree with each other to the 16-bit drift."""
     bank = _bank(fx, "f16")
     eng = fx["m2"].engines()[1]
