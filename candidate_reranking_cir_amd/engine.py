@@ -20,8 +20,9 @@ nlvr_encoder.py:414-476 / 777-908, blip_stage2.py:101-136.
 """
 from __future__ import annotations
 
+import warnings
 import weakref
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -81,6 +82,16 @@ def _ln(x, gamma, beta, eps, dt, sdt, residual=None, need_stream=True, split8=Fa
         y, _ = ops.layernorm(x, gamma, beta, eps, residual=residual, want32=True, dtype16=None, stream_dtype=sdt)
         return y, y
     return ops.layernorm(x, gamma, beta, eps, residual=residual, want32=need_stream, dtype16=dt, stream_dtype=sdt)
+
+
+def _attend(q, k, v, scale, mask, dt, split8, lead):
+    """Self-attention context as the output projection's A operand under the leading shape `lead`: split8 rows written by the fp32
+    attention kernel itself (text32 mode), or a fresh `dt` tensor (*lead, D) filled by `ops.attention`."""
+    if split8:
+        return ops.attention_split8(q, k, v, scale, mask).view(*lead)
+    ctx = torch.empty(q.shape, dtype=dt, device=q.device)
+    ops.attention(q, k, v, ctx, scale, mask)
+    return ctx.view(*lead, q.shape[-1])
 
 
 def additive_self_mask(attention_mask: torch.Tensor) -> torch.Tensor:
@@ -279,15 +290,10 @@ class MedEngine:
         emask = additive_encoder_mask(enc_mask).view(q_n, 1, n) if enc_mask is not None else None
         enc2 = enc16.reshape(q_n * n, enc16.shape[2])
         s8 = self.split == 8       # text32 on split8 rows: the LayerNorm / attention / fc1 kernels write the next GEMM's operand themselves
-        ctx = None if s8 else torch.empty((q_n, 1, l, d), dtype=dt, device=hs.device)
-        ctx_x = ctx if (xdt == dt and not s8) else torch.empty((q_n, 1, l, d), dtype=xdt, device=hs.device)
+        ctx_x = torch.empty((q_n, 1, l, d), dtype=xdt, device=hs.device)
         for ly in self.layers:
             qkv = ops.gemm(h16, ly["wqkv"], ly["bqkv"]).view(q_n, 1, l, 3 * d)
-            if s8:
-                ctx_op = ops.attention_split8(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], scale, smask).view(r)
-            else:
-                ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], ctx, scale, smask)   # med.py:158-240
-                ctx_op = ctx.view(r, d)
+            ctx_op = _attend(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], scale, smask, dt, s8, (r,))   # med.py:158-240
             t = ops.gemm(ctx_op, ly["wo"], ly["bo"], residual=hs, out_dtype=sdt)
             a_s, a16 = _ln(t, ly["g1"], ly["b1"], eps, xdt, sdt)                                       # med.py:250-253 (operand copy feeds cross-Q only)
             qc = ops.gemm(a16, ly["wq"], ly["bq"]).view(q_n, 1, l, d)
@@ -305,6 +311,24 @@ class MedEngine:
 
 
 # =================================================================================================
+class LayerPlan(NamedTuple):
+    """One fusion layer of a `Plan`."""
+    cls_only: bool          # per-token work on the CLS rows only (the trimmed last layer)
+    cross: str              # cross-attention path: "cls_fold", "fold32", "fold_long", "projected" or "bank"
+    sdt: torch.dtype        # residual-stream type the layer receives ...
+    sdt_out: torch.dtype    # ... and the one its last LayerNorm writes (the next layer's)
+
+
+class Plan(NamedTuple):
+    """What `NlvrEngine.plan` returns.  Hashable, no tensors: with the argument shapes it is the key of a captured graph."""
+    layers: Tuple[LayerPlan, ...]
+    kv_chunk: int           # candidates per K|V + cross-attention chunk of the "projected" layers (0 = all at once)
+    fallback: bool          # the call counts in `fold_fallbacks`: long captions on the projected path although the fold is on
+
+
+SCALE = 64 ** -0.5          # every attention head of the text side is 64 wide
+
+
 class NlvrEngine:
     """Stage-II two-branch BERT + cls_head (nlvr_encoder.py:414-476, 777-908; blip_stage2.py:50-54, 101-136).
 
@@ -316,6 +340,10 @@ class NlvrEngine:
     merge_layer ones - `fold_merge=False` keeps dense0/dense1 and merge_layer as separate GEMMs);
     twin LayerNorm with the shared merged tensor; FFN on both branches as one M = 2R GEMM pair.
     Layer 0's self-attention block is candidate-independent and runs once per QUERY.
+
+    Which of these launches a call issues is decided in one place: `plan` maps the call's sizes and the live switches (plain attributes,
+    set between calls: `trim_last`, `kv_chunk`, `fold_cls_kv`, `fold_cross_kv`, `fold_long`, `stream32_from`, `cls_fold`) to a `Plan` before
+    the first launch; `forward` executes it and `forward_graphed` keys its captures with it.  A new host-side switch belongs in `plan`.
     """
 
     def __init__(self, sd: SD, geo: BertGeometry, dtype: torch.dtype, device, prefix: str = "text_encoder.", fold_merge: bool = True,
@@ -341,6 +369,8 @@ class NlvrEngine:
         # it measures faster than the projected path at 33-48 tokens and slower at 49-64 (LABNOTES.md section 14); a default per length is a later
         # change (BLIP_NLVR.set_long_caption_fold).
         self.fold_long = False
+        self.stream32_from = None    # layers >= this index keep their residual stream in fp32 (None: `stream_dtype` everywhere)
+        self._graphs = {}            # graph_key -> ScoreGraph, in recency order (`forward_graphed`)
         e = prefix + "embeddings."
         self.word, self.posemb = _f32(sd[e + "word_embeddings.weight"], device), _f32(sd[e + "position_embeddings.weight"], device)
         self.ge, self.be = _f32(sd[e + "LayerNorm.weight"], device), _f32(sd[e + "LayerNorm.bias"], device)
@@ -413,21 +443,36 @@ class NlvrEngine:
             _mark_split(self.split, self.layers, self.wc0)
 
     # ---------------------------------------------------------------------------------------------
-    def _self_block(self, ly, h32, h16, items, l, smask, sdt=None):
-        """Twin self-attention + LayerNormA/B on (2, items*L, D) hidden states (nlvr_encoder.py:427-433, 262-264).  The 16-bit
-        copy of the result feeds the cross-attention query projection only: it is written in `xdtype`."""
-        d, dt, eps = self.geo.hidden_size, self.dtype, self.geo.layer_norm_eps
-        sdt = sdt or self.stream_dtype
-        r = items * l
-        qkv = ops.gemm(h16, ly["wqkv"], ly["bqkv"]).view(2, items, l, 3 * d)
-        if self.split == 8:       # the fp32 attention writes the output projection's split8 operand itself
-            ctx_op = ops.attention_split8(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], 64 ** -0.5, smask.unsqueeze(0).expand(2, items, l)).view(2, r)
-        else:
-            ctx = torch.empty((2, items, l, d), dtype=dt, device=h32.device)
-            ops.attention(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], ctx, 64 ** -0.5, smask.unsqueeze(0).expand(2, items, l))
-            ctx_op = ctx.view(2, r, d)
-        t = ops.gemm(ctx_op, ly["wo"], ly["bo"], residual=h32, out_dtype=sdt)
-        return _ln(t, ly["g1"], ly["b1"], eps, self.xdtype, sdt)
+    def plan(self, l: int, n: int, dv: int, masked: bool, bank: Optional[Tuple[bool, ...]] = None) -> Plan:
+        """Every host-side decision of a forward for captions of `l` tokens against `n` keys of width `dv`, with (`masked`) or without a
+        candidate mask, on candidate tokens (`bank` None) or a K/V bank (`bank[i]`: the bank holds no K|V of layer i): a pure function of
+        these and of the live switches (class docstring)."""
+        d, dt, s32, last = self.geo.hidden_size, self.dtype, self.stream32_from, len(self.layers) - 1
+        sd = lambda i: torch.float32 if (s32 is not None and i >= s32 and dt != torch.float32) else self.stream_dtype
+        layers = []
+        for i, ly in enumerate(self.layers):
+            cls_only = self.trim_last and i == last and i > 0
+            no_kv = bank is not None and bank[i]
+            foldable = bank is None and self.fold_cross_kv and "wkt" in ly and not cls_only and dv == d
+            if cls_only and not masked and self.cls_fold is not None and self.fold_cls_kv and (bank is None or no_kv):
+                cross = "cls_fold"
+            elif no_kv:
+                raise ValueError("this K/V bank was built with the last layer folded (no K|V of that layer): rebuild it with fold_cls_kv = False")
+            elif foldable and l <= 32 and n <= 608:
+                cross = "fold32"
+            elif foldable and self.fold_long and 33 <= l <= 64 and n <= 224:
+                cross = "fold_long"
+            else:
+                cross = "projected" if bank is None else "bank"
+            layers.append(LayerPlan(cls_only, cross, sd(i), sd(i + 1)))
+        # counted where layer 1 projects although the engine folds.  Bookkeeping, not a launch: it makes the graph key finer than the
+        # launches need (fold_cross_kv off at 40 tokens issues the default's launches under a key of its own - one slot of the LRU)
+        fallback = last >= 1 and layers[1].cross == "projected" and self.fold_cross_kv and "wkt" in self.layers[1] and l > 32
+        return Plan(tuple(layers), self.kv_chunk, fallback)
+
+    def graph_key(self, ids_shape, cand_shape, cand_dtype) -> tuple:
+        """What a captured graph of `forward` is valid for: the problem and its plan."""
+        return (tuple(ids_shape), tuple(cand_shape), cand_dtype, self.plan(ids_shape[1], cand_shape[1], cand_shape[2], False))
 
     @torch.no_grad()
     def build_kv_bank(self, bank16: torch.Tensor, chunk: int = 512) -> list:
@@ -454,15 +499,16 @@ class NlvrEngine:
 
     def forward_graphed(self, input_ids, attention_mask, z_t32, cand16, qidx) -> torch.Tensor:
         """`forward` through a captured HIP graph per problem shape (ScoreGraph); at most 8 are kept (least recently used dropped).
-        A capture freezes every host-side branch of `forward`: the attributes that decide one (live A/B switches) are part of the key, so
-        changing one takes a new capture instead of replaying the old path.  Replays share the graph's static buffers: one stream at a
-        time.  With bench.py's per-launch event profiling on (ops.PROFILE_*) nothing is captured - events would be recorded inside."""
+        A capture freezes every host-side branch of `forward`.  Those branches are the plan's and nothing else's, and the plan is part of the
+        key (`graph_key`): changing a live A/B switch takes a new capture where it changes the plan, instead of replaying the old path.
+        `lib.set_tuning` is not in the plan: the kernel selection in force at capture time stays frozen into the graph.  Replays share the
+        graph's static buffers: one stream at a time.  With bench.py's per-launch event profiling on (ops.PROFILE_*) nothing is captured -
+        events would be recorded inside."""
         if ops.PROFILE_GEMM is not None or ops.PROFILE_ATTN is not None:
             return self.forward(input_ids, attention_mask, z_t32, cand16, qidx)
-        graphs = self.__dict__.setdefault("_graphs", {})
+        graphs = self._graphs
         z_t32 = z_t32.float().contiguous()
-        key = (tuple(input_ids.shape), tuple(cand16.shape), cand16.dtype, self.kv_chunk, self.trim_last, self.fold_cls_kv, self.fold_cross_kv,
-               getattr(self, "stream32_from", None), self.fold_long)
+        key = self.graph_key(input_ids.shape, cand16.shape, cand16.dtype)
         g = graphs.pop(key, None)
         if g is None:
             if len(graphs) >= 8:
@@ -471,131 +517,136 @@ class NlvrEngine:
         graphs[key] = g                                   # (re-)inserted last: the dict's order is the recency order
         return g(input_ids, attention_mask, z_t32, cand16, qidx)
 
-    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, z_t32: torch.Tensor, cand16: Optional[torch.Tensor],
-                qidx: torch.Tensor, cand_mask: Optional[torch.Tensor] = None, taps: Optional[list] = None,
-                kv_bank: Optional[list] = None, cand_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """ids/mask (Q, L), z_t (Q, L, D) fp32, candidate tokens (T, N, Dv) 16-bit, qidx (T,) int64 = the
-        query each candidate belongs to -> logits (T, 2) fp32 (column 0 is the score).
-        With `kv_bank` (from build_kv_bank) and `cand_rows` (T,) int64 bank rows, the per-candidate K|V GEMM is
-        skipped and cross-attention reads K/V straight from the bank (cand16 is not used)."""
+    # --------------------------------------------------------------------------------------------- the blocks `forward` schedules
+    def _self_block(self, ly, h32, h16, items, l, smask, sdt, lq=None):
+        """Twin self-attention + LayerNormA/B on (2, items*L, D) hidden states (nlvr_encoder.py:427-433, 262-264).  The 16-bit
+        copy of the result feeds the cross-attention query projection only: it is written in `xdtype`.  `lq = 1`: the CLS-only layer -
+        every token is still a key / value, the query, the context and the residual are the CLS rows (a strided view of `h32`)."""
+        d, eps, lq = self.geo.hidden_size, self.geo.layer_norm_eps, lq or l
+        qkv = ops.gemm(h16, ly["wqkv"], ly["bqkv"]).view(2, items, l, 3 * d)
+        ctx_op = _attend(qkv[:, :, :lq, :d], qkv[..., d:2 * d], qkv[..., 2 * d:], SCALE, smask.unsqueeze(0).expand(2, items, l), self.dtype,
+                         self.split == 8, (2, items * lq))
+        t = ops.gemm(ctx_op, ly["wo"], ly["bo"], residual=h32 if lq == l else h32.view(2, items, l, d)[:, :, 0, :], out_dtype=sdt)
+        return _ln(t, ly["g1"], ly["b1"], eps, self.xdtype, sdt)
+
+    def _query_block(self, input_ids, attention_mask, z_t32, qidx, t_n, sdt):
+        """Embeddings and layer 0's self-attention block: they depend on (z_t, caption) only, so they run once per QUERY and are then
+        expanded to the candidates -> (stream rows, cross-Q operand rows) (2, T L, D) and the (T, L) self-attention key mask."""
         geo, dt, xdt = self.geo, self.dtype, self.xdtype
-        # residual-stream storage per layer: `stream_dtype` everywhere, or fp32 from layer `stream32_from` on (the layers nearest the
-        # logits; DESIGN section 2) - a layer's last LayerNorm writes the stream of the NEXT layer's type
-        s32 = getattr(self, "stream32_from", None)
-        sd = lambda i: torch.float32 if (s32 is not None and i >= s32 and dt != torch.float32) else self.stream_dtype
-        sdt = sd(0)
-        q_n, l = input_ids.shape
-        if kv_bank is not None:
-            if getattr(kv_bank, "engine", None) is None or kv_bank.engine() is not self:
-                raise RuntimeError("kv_bank was not built by this engine: the model's parameters were written (or its precision changed) since "
-                                   "build_kv_bank - its K/V are projections of the old weights; build the bank again")
-            cand_rows = cand_rows.to(torch.int64).contiguous()
-            t_n, n = cand_rows.shape[0], kv_bank[0].shape[1]
-        else:
-            t_n, n = cand16.shape[0], cand16.shape[1]
-        d, eps, scale = geo.hidden_size, geo.layer_norm_eps, 64 ** -0.5
-        r = t_n * l
-        emb32, _ = ops.embed_layernorm(input_ids, self.word, self.posemb, self.ge, self.be, eps, dt)   # nlvr_encoder.py:880-886
+        (q_n, l), d = input_ids.shape, geo.hidden_size
+        emb32, _ = ops.embed_layernorm(input_ids, self.word, self.posemb, self.ge, self.be, geo.layer_norm_eps, dt)   # nlvr_encoder.py:880-886
         if tuple(z_t32.shape) != tuple(emb32.shape):
             raise AssertionError("left and right inputs shall be the same shape")                         # nlvr_encoder.py:891
         hq32 = torch.stack([z_t32.reshape(q_n * l, d).float(), emb32.view(q_n * l, d)])                   # (2, Q*L, D): [z_t, emb] :892
         hq_s = hq32 if sdt == torch.float32 else ops.gather_rows(hq32.view(2 * q_n * l, d), None, sdt).view(2, q_n * l, d)
         hq16 = hq_s if dt == sdt else ops.gather_rows(hq32.view(2 * q_n * l, d), None, dt).view(2, q_n * l, d)
         smask_q = additive_self_mask(attention_mask)                                                     # (Q, L)
-        # layer 0 self-attention block depends only on (z_t, caption): once per query, then expand to candidates
         a_sq, a16q = self._self_block(self.layers[0], hq_s, hq16, q_n, l, smask_q, sdt)
         both = torch.cat([qidx, qidx + q_n])                                                              # rows of (2*Q, L*D)
-        a32 = ops.gather_rows(a_sq.view(2 * q_n, l * d), both, sdt).view(2, r, d)
-        a16 = a32 if xdt == sdt else ops.gather_rows(a16q.view(2 * q_n, l * d), both, xdt).view(2, r, d)
-        smask = ops.gather_rows(_pad8(smask_q), qidx, torch.float32)[:, :l]                             # (T, L) view
+        a32 = ops.gather_rows(a_sq.view(2 * q_n, l * d), both, sdt).view(2, t_n * l, d)
+        a16 = a32 if xdt == sdt else ops.gather_rows(a16q.view(2 * q_n, l * d), both, xdt).view(2, t_n * l, d)
+        return a32, a16, ops.gather_rows(_pad8(smask_q), qidx, torch.float32)[:, :l]
+
+    def _cross_block(self, ly, lp: LayerPlan, a16, cc, tok, emask2d, rows, kv, kv_chunk):
+        """Cross-attention query projection and the cross-attention on the layer's planned path -> [c0 | c1] rows (T, Lq, 2, D).  `tok`: the
+        candidate tokens (T, N, Dv), or the bank's (n_index, N, Dv) with the bank rows `rows` and the layer's K|V `kv`."""
+        d, (t_n, l), n = self.geo.hidden_size, cc.shape[:2], tok.shape[1]
+        qraw = ops.gemm(a16, ly["wq"], ly["bq"])                                                        # (2, T Lq, D)
+        qc = qraw.view(2, t_n, -1, d).permute(1, 0, 2, 3)                                                 # (T, 2, Lq, D) view
+        ccl = cc if not lp.cls_only else torch.empty((t_n, 1, 2, d), dtype=self.xdtype, device=cc.device)
+        emask = None if emask2d is None else emask2d.view(t_n, 1, n).expand(t_n, 2, n)
+        if lp.cross == "cls_fold":
+            self._cross_cls_fold(qc, ccl, tok, rows)
+        elif lp.cross in ("fold32", "fold_long"):
+            fold = ops.cross_attention_folded if lp.cross == "fold32" else ops.cross_attention_folded_long
+            fold(qraw, tok, ly["wkt"], ly["wvp"], ly["bvf"], ccl, l, SCALE, heads=self.geo.num_attention_heads, mask=emask2d)
+        elif lp.cross == "projected":
+            self._cross_projected(ly, qc, ccl, tok, emask, kv_chunk)
+        else:                                                                                             # (n_index, N, 4, D) bank
+            kv = kv.view(-1, n, 4, d)
+            ops.attention(qc, kv[:, :, 0::2].permute(0, 2, 1, 3), kv[:, :, 1::2].permute(0, 2, 1, 3), ccl.permute(0, 2, 1, 3), SCALE, emask,
+                          kv_index=rows)
+        return ccl
+
+    def _cross_cls_fold(self, qc, ccl, tok, rows):
+        """One query row per (branch, head): scores = (W_k^T q) . x_j, context = W_v (sum_j p_j x_j) + b_v - the 4 D x Dv projection of all
+        T * N candidate tokens of this layer is never formed (nlvr_encoder.py:321-344)."""
+        f, h_n, t_n, dv = self.cls_fold, self.geo.num_attention_heads, ccl.shape[0], tok.shape[2]
+        qp = f["qp"].get(t_n)
+        if qp is None:                                                                                    # rows >= 2H stay zero
+            qp = f["qp"][t_n] = torch.zeros((t_n, 32, dv), dtype=self.xdtype, device=ccl.device)
+        q2 = qc.permute(1, 0, 2, 3).reshape(2, t_n, h_n, 64)                                              # view of the (2, T, D) GEMM result
+        for b in (0, 1):
+            ops.gemm(q2[b].permute(1, 0, 2), f["wkt"][b], None, out=qp[:, b * h_n:(b + 1) * h_n, :].permute(1, 0, 2))
+        o = ops.cls_cross_attention(tok, qp, SCALE, x_index=rows)
+        ops.gemm(o[:, :2 * h_n, :].permute(1, 0, 2), f["wv"], f["bv"], out=ccl.view(t_n, 2 * h_n, 64).permute(1, 0, 2))
+
+    def _cross_projected(self, ly, qc, ccl, tok, emask, kv_chunk):
+        """K|V projection + cross-attention, optionally in candidate chunks (`kv_chunk`; measured: no gain from keeping a chunk's K|V in
+        the Infinity Cache, so the default is one launch each)."""
+        d, (t_n, n, dv) = self.geo.hidden_size, tok.shape
+        cand2 = tok.reshape(t_n * n, dv)
+        step_c = kv_chunk if kv_chunk > 0 else t_n
+        for c0 in range(0, t_n, step_c):
+            c1 = min(c0 + step_c, t_n)
+            kv = ops.gemm(cand2[c0 * n:c1 * n], ly["wkv"], ly["bkv"]).view(c1 - c0, n, 4, d)             # [K0 V0 K1 V1]
+            ops.attention(qc[c0:c1], kv[:, :, 0::2].permute(0, 2, 1, 3), kv[:, :, 1::2].permute(0, 2, 1, 3),
+                          ccl[c0:c1].permute(0, 2, 1, 3), SCALE, None if emask is None else emask[c0:c1])   # nlvr_encoder.py:321-344
+
+    def _merge_ffn(self, ly, lp: LayerPlan, ccl, a32, rq):
+        """Merge of the two branches' cross-attention outputs, LayerNormA/B(m + att_b), the shared FFN, the layer's last LayerNorm ->
+        next hidden states (stream copy in `lp.sdt_out`, operand copy), each (2, rq, D)."""
+        d, dt, eps, xdt, s8 = self.geo.hidden_size, self.dtype, self.geo.layer_norm_eps, self.xdtype, self.split == 8
+        if "wd" in ly:                                                                                    # unfolded merge_layer
+            dd = torch.empty((rq, 2, d), dtype=xdt, device=ccl.device)
+            ops.gemm(ccl.view(rq, 2, d).permute(1, 0, 2), ly["wd"], ly["bd"], out=dd.permute(1, 0, 2))
+            m = ops.gemm(dd.view(rq, 2 * d), ly["wm"], ly["bm"], out_dtype=lp.sdt)
+        else:
+            m = ops.gemm(ccl.view(rq, 2 * d), ly["wm"], ly["bm"], out_dtype=lp.sdt)                      # :252-260
+        x32, x16 = _ln(m, ly["g2"], ly["b2"], eps, dt, lp.sdt, residual=a32, split8=s8)                  # LayerNormA/B(m + att_b)
+        f = ops.gemm(x16.view(2 * rq, d) if not s8 else x16.view(2 * rq), ly["w1"], ly["c1"], act=ops.ACT_GELU)   # shared FFN :469-476
+        t = ops.gemm(f, ly["w2"], ly["c2"], residual=x32.view(2 * rq, d), out_dtype=lp.sdt)
+        h32, h16 = _ln(t, ly["g3"], ly["b3"], eps, dt, lp.sdt_out, split8=s8)
+        return h32.view(2, rq, d), (h16.view(2, rq, d) if not s8 else h16.view(2, rq))
+
+    def forward(self, input_ids: torch.Tensor, attention_mask: torch.Tensor, z_t32: torch.Tensor, cand16: Optional[torch.Tensor],
+                qidx: torch.Tensor, cand_mask: Optional[torch.Tensor] = None, taps: Optional[list] = None,
+                kv_bank: Optional[list] = None, cand_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ids/mask (Q, L), z_t (Q, L, D) fp32, candidate tokens (T, N, Dv) 16-bit, qidx (T,) int64 = the
+        query each candidate belongs to -> logits (T, 2) fp32 (column 0 is the score).
+        With `kv_bank` (from build_kv_bank) and `cand_rows` (T,) int64 bank rows, the per-candidate K|V GEMM is
+        skipped and cross-attention reads K/V straight from the bank (cand16 is not used).  Executes `plan`, made before the first launch."""
+        d, l = self.geo.hidden_size, input_ids.shape[1]
+        if kv_bank is not None:
+            if getattr(kv_bank, "engine", None) is None or kv_bank.engine() is not self:
+                raise RuntimeError("kv_bank was not built by this engine: the model's parameters were written (or its precision changed) since "
+                                   "build_kv_bank - its K/V are projections of the old weights; build the bank again")
+            bank, tok, cand_rows = tuple(kv is None for kv in kv_bank), kv_bank.tokens, cand_rows.to(torch.int64).contiguous()
+            t_n, n = cand_rows.shape[0], kv_bank[0].shape[1]
+        else:
+            bank, tok, cand_rows, (t_n, n), kv_bank = None, cand16, None, cand16.shape[:2], [None] * len(self.layers)
+        plan = self.plan(l, n, tok.shape[2], cand_mask is not None, bank)
+        a32, a16, smask = self._query_block(input_ids, attention_mask, z_t32, qidx, t_n, plan.layers[0].sdt)
+        self.fold_fallbacks += plan.fallback               # (counted once the inputs are accepted, as when the count sat in layer 1)
+        if plan.fallback and self.fold_fallbacks == 1:
+            warnings.warn(f"captions of {l} tokens (> 32): the cross-attention runs the projected K|V path for this batch (~8 % of a step slower than "
+                          "the query-side fold at 224 px); NlvrEngine.fold_fallbacks counts such calls; 33-64 tokens against <= 224 keys can take the "
+                          "long-caption fold instead: BLIP_NLVR.set_long_caption_fold()", stacklevel=3)
         emask2d = additive_encoder_mask(cand_mask).view(t_n, n) if cand_mask is not None else None       # (T, N): the folded kernels' form
-        emask = emask2d.view(t_n, 1, n).expand(t_n, 2, n) if cand_mask is not None else None
-        cand2 = cand16.reshape(t_n * n, cand16.shape[2]) if kv_bank is None else None
-        cc = torch.empty((t_n, l, 2, d), dtype=xdt, device=z_t32.device)
+        cc = torch.empty((t_n, l, 2, d), dtype=self.xdtype, device=z_t32.device)
         h32 = h16 = None
-        s8 = self.split == 8      # text32 on split8 rows: LayerNorm / attention / fc1 kernels write the next GEMM's operand themselves
-        last = len(self.layers) - 1
-        for i, ly in enumerate(self.layers):
-            # Only the two CLS rows of the last layer reach cls_head (nlvr_encoder.py:906-908): after its self-attention
-            # (which still needs every token as key/value) everything per-token runs on 1 row per candidate instead of L.
-            cls_only = self.trim_last and i == last and i > 0
-            sdt = sd(i)                                    # this layer's stream type (h32 arrives in it)
-            lq = 1 if cls_only else l
-            rq = t_n * lq
-            if cls_only:
-                qkv = ops.gemm(h16, ly["wqkv"], ly["bqkv"]).view(2, t_n, l, 3 * d)
-                if s8:
-                    ctx_op = ops.attention_split8(qkv[:, :, :1, :d], qkv[..., d:2 * d], qkv[..., 2 * d:], scale, smask.unsqueeze(0).expand(2, t_n, l)).view(2, t_n)
-                else:
-                    ctx = torch.empty((2, t_n, 1, d), dtype=dt, device=h32.device)
-                    ops.attention(qkv[:, :, :1, :d], qkv[..., d:2 * d], qkv[..., 2 * d:], ctx, scale, smask.unsqueeze(0).expand(2, t_n, l))
-                    ctx_op = ctx.view(2, t_n, d)
-                t = ops.gemm(ctx_op, ly["wo"], ly["bo"], residual=h32.view(2, t_n, l, d)[:, :, 0, :], out_dtype=sdt)
-                a32, a16 = _ln(t, ly["g1"], ly["b1"], eps, xdt, sdt)
-            elif i > 0:
-                a32, a16 = self._self_block(ly, h32, h16, t_n, l, smask, sdt)
-            qraw = ops.gemm(a16, ly["wq"], ly["bq"])                                                    # (2, T Lq, D)
-            qc = qraw.view(2, t_n, lq, d).permute(1, 0, 2, 3)                                             # (T, 2, Lq, D) view
-            ccl = cc if not cls_only else torch.empty((t_n, 1, 2, d), dtype=xdt, device=cc.device)
-            fold = cls_only and emask is None and self.cls_fold is not None and self.fold_cls_kv and (kv_bank is None or kv_bank[i] is None)
-            if kv_bank is not None and kv_bank[i] is None and not fold:
-                raise ValueError("this K/V bank was built with the last layer folded (no K|V of that layer): rebuild it with fold_cls_kv = False")
-            if fold:
-                # one query row per (branch, head): scores = (W_k^T q) . x_j, context = W_v (sum_j p_j x_j) + b_v - the
-                # 4 D x Dv projection of all T * N candidate tokens of this layer is never formed (nlvr_encoder.py:321-344)
-                tok = cand16 if kv_bank is None else kv_bank.tokens                                       # (T, N, Dv) or the index bank + row index
-                f, h_n, dv = self.cls_fold, geo.num_attention_heads, tok.shape[2]
-                qp = f["qp"].get(t_n)
-                if qp is None:                                                                            # rows >= 2H stay zero
-                    qp = f["qp"][t_n] = torch.zeros((t_n, 32, dv), dtype=xdt, device=cc.device)
-                q2 = qc.permute(1, 0, 2, 3).reshape(2, t_n, h_n, 64)                                      # view of the (2, T, D) GEMM result
-                for b in (0, 1):
-                    ops.gemm(q2[b].permute(1, 0, 2), f["wkt"][b], None, out=qp[:, b * h_n:(b + 1) * h_n, :].permute(1, 0, 2))
-                o = ops.cls_cross_attention(tok, qp, scale, x_index=None if kv_bank is None else cand_rows)
-                ops.gemm(o[:, :2 * h_n, :].permute(1, 0, 2), f["wv"], f["bv"], out=ccl.view(t_n, 2 * h_n, 64).permute(1, 0, 2))
-            elif (kv_bank is None and self.fold_cross_kv and "wkt" in ly and not cls_only and l <= 32 and n <= 608
-                  and cand16.shape[2] == d):
-                ops.cross_attention_folded(qraw, cand16, ly["wkt"], ly["wvp"], ly["bvf"], ccl, l, scale, heads=geo.num_attention_heads, mask=emask2d)
-            elif (kv_bank is None and self.fold_long and self.fold_cross_kv and "wkt" in ly and not cls_only and 33 <= l <= 64 and n <= 224
-                  and cand16.shape[2] == d):
-                ops.cross_attention_folded_long(qraw, cand16, ly["wkt"], ly["wvp"], ly["bvf"], ccl, l, scale, heads=geo.num_attention_heads, mask=emask2d)
-            elif kv_bank is None:
-                if self.fold_cross_kv and "wkt" in ly and l > 32 and i == 1:
-                    self.fold_fallbacks += 1
-                    if self.fold_fallbacks == 1:
-                        import warnings
-                        warnings.warn(f"captions of {l} tokens (> 32): the cross-attention runs the projected K|V path for this batch (~8 % of a step slower than "
-                                      "the query-side fold at 224 px); NlvrEngine.fold_fallbacks counts such calls; 33-64 tokens against <= 224 keys can take the "
-                                      "long-caption fold instead: BLIP_NLVR.set_long_caption_fold()", stacklevel=3)
-                # K|V projection + cross-attention, optionally in candidate chunks (`kv_chunk`; measured: no gain from
-                # keeping a chunk's K|V in the Infinity Cache, so the default is one launch each)
-                step_c = self.kv_chunk if self.kv_chunk > 0 else t_n
-                for c0 in range(0, t_n, step_c):
-                    c1 = min(c0 + step_c, t_n)
-                    kv = ops.gemm(cand2[c0 * n:c1 * n], ly["wkv"], ly["bkv"]).view(c1 - c0, n, 4, d)     # [K0 V0 K1 V1]
-                    ops.attention(qc[c0:c1], kv[:, :, 0::2].permute(0, 2, 1, 3), kv[:, :, 1::2].permute(0, 2, 1, 3),
-                                  ccl[c0:c1].permute(0, 2, 1, 3), scale, None if emask is None else emask[c0:c1])   # nlvr_encoder.py:321-344
-            else:
-                kv = kv_bank[i].view(-1, n, 4, d)                                                         # (n_index, N, 4, D) bank
-                ops.attention(qc, kv[:, :, 0::2].permute(0, 2, 1, 3), kv[:, :, 1::2].permute(0, 2, 1, 3),
-                              ccl.permute(0, 2, 1, 3), scale, emask, kv_index=cand_rows)
-            if "wd" in ly:                                                                                # unfolded merge_layer
-                dd = torch.empty((rq, 2, d), dtype=xdt, device=cc.device)
-                ops.gemm(ccl.view(rq, 2, d).permute(1, 0, 2), ly["wd"], ly["bd"], out=dd.permute(1, 0, 2))
-                m = ops.gemm(dd.view(rq, 2 * d), ly["wm"], ly["bm"], out_dtype=sdt)
-            else:
-                m = ops.gemm(ccl.view(rq, 2 * d), ly["wm"], ly["bm"], out_dtype=sdt)                     # :252-260
-            x32, x16 = _ln(m, ly["g2"], ly["b2"], eps, dt, sdt, residual=a32, split8=s8)                 # LayerNormA/B(m + att_b)
-            f = ops.gemm(x16.view(2 * rq, d) if not s8 else x16.view(2 * rq), ly["w1"], ly["c1"], act=ops.ACT_GELU)   # shared FFN :469-476
-            t = ops.gemm(f, ly["w2"], ly["c2"], residual=x32.view(2 * rq, d), out_dtype=sdt)
-            h32, h16 = _ln(t, ly["g3"], ly["b3"], eps, dt, sd(i + 1), split8=s8)
-            h32, h16 = h32.view(2, rq, d), (h16.view(2, rq, d) if not s8 else h16.view(2, rq))
+        for ly, lp, kv in zip(self.layers, plan.layers, kv_bank):
+            lq = 1 if lp.cls_only else l
+            if h32 is not None:                # (layer 0's self-attention block ran per query, above)
+                a32, a16 = self._self_block(ly, h32, h16, t_n, l, smask, lp.sdt, lq)
+            ccl = self._cross_block(ly, lp, a16, cc, tok, emask2d, cand_rows, kv, plan.kv_chunk)
+            h32, h16 = self._merge_ffn(ly, lp, ccl, a32, t_n * lq)
             if taps is not None:
                 hv = h32.view(2, t_n, lq, d)
                 taps.append((hv[0, :, 0, :8].float(), hv[1, :, 0, :8].float()))
-        l = 1 if (self.trim_last and last > 0) else l
-        hcls = h32 if s8 else h16                                                                         # (split8: the fp32 stream copy holds the same values)
-        hid = hcls.view(2, t_n, l, d)[:, :, 0, :].permute(1, 0, 2).reshape(t_n, 2 * d)                    # cat(CLS_0, CLS_1) :906-908
+        lq = 1 if plan.layers[-1].cls_only else l
+        hcls = h32 if self.split == 8 else h16                                                            # (split8: the fp32 stream copy holds the same values)
+        hid = hcls.view(2, t_n, lq, d)[:, :, 0, :].permute(1, 0, 2).reshape(t_n, 2 * d)                   # cat(CLS_0, CLS_1) :906-908
         y = ops.gemm(hid, self.wc0, self.bc0, act=ops.ACT_RELU)                                           # blip_stage2.py:50-52
         return ops.small_linear(y, self.wc2, self.bc2)                                                    # blip_stage2.py:53
 

@@ -369,6 +369,66 @@ def test_hip_graph_scoring_is_bit_identical_and_follows_the_engine():
     assert torch.equal(m.enable_graphs(64).score(*cases[0]), ref) and m.engines()[1] is not eng
 
 
+def test_hip_graph_key_follows_every_live_switch():
+    """The key of a captured graph is the problem's shapes and its launch plan (`NlvrEngine.graph_key`): for each live switch in turn the
+    graphed score equals the direct score under the same setting bit for bit, and a new graph is captured exactly where the switch changes
+    the plan - everywhere but `fold_long` at 32 tokens, which only captions of 33-64 tokens look at."""
+    import warnings
+    from candidate_reranking_cir_amd import synthetic
+    from candidate_reranking_cir_amd.config import BertGeometry, VitGeometry
+    from candidate_reranking_cir_amd.blip_stage2 import BLIP_NLVR
+    dev = torch.device("cuda")
+    vit = VitGeometry(image_size=64, patch_size=16, width=768, depth=1, num_heads=12)
+    torch.manual_seed(0)
+    m = BLIP_NLVR(BertGeometry(num_hidden_layers=4), vit_geometry=vit, tokenizer=synthetic.HashTokenizer()).to(dev).eval()
+    g = torch.Generator(device="cpu").manual_seed(3)
+    k, n = 2, 197
+    cand = (torch.randn((k, n, 768), generator=g) * 0.5).to(dev).half()
+    qidx = torch.zeros(k, dtype=torch.int64, device=dev)
+    cases = {}
+    for l in (32, 40):
+        ids = torch.randint(1000, 20000, (1, l), generator=g).to(dev)
+        cases[l] = (torch.randn((1, l, 768), generator=g).to(dev), ids, torch.ones_like(ids), cand, qidx)
+
+    def both(l):
+        graphed = m.enable_graphs(64).score(*cases[l])
+        direct = m.enable_graphs(0).score(*cases[l])
+        m.enable_graphs(64)
+        return graphed, direct
+
+    def attr(name, value):
+        return lambda: setattr(m.engines()[1], name, value)
+
+    switches = [("fold_long", lambda: m.set_long_caption_fold(True), lambda: m.set_long_caption_fold(False)),
+                ("fold_cross_kv", attr("fold_cross_kv", False), attr("fold_cross_kv", True)),
+                ("fold_cls_kv", attr("fold_cls_kv", False), attr("fold_cls_kv", True)),
+                ("trim_last", attr("trim_last", False), attr("trim_last", True)),
+                ("kv_chunk", attr("kv_chunk", 1), attr("kv_chunk", 0)),
+                ("stream32_from", lambda: m.set_text_stream32_from(2), lambda: m.set_text_stream32_from(None))]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                        # (40 tokens on the projected path warn once per engine)
+        default = {l: m.engines()[1].plan(l, n, 768, False) for l in cases}
+        for l in cases:
+            graphed, direct = both(l)
+            assert torch.equal(graphed, direct)
+        base = set(m.engines()[1]._graphs)
+        assert len(base) == 2
+        for name, on, off in switches:
+            on()
+            eng = m.engines()[1]                               # (set_text_stream32_from packs a new engine: no graphs yet)
+            for l in cases:
+                before = len(eng._graphs)
+                changed = not (name == "fold_long" and l == 32)
+                assert (eng.plan(l, n, 768, False) != default[l]) == changed, (name, l)
+                graphed, direct = both(l)
+                assert torch.equal(graphed, direct), (name, l)
+                assert len(eng._graphs) == before + int(changed), (name, l)
+                assert torch.equal(m.score(*cases[l]), direct) and len(eng._graphs) == before + int(changed)   # and replays it after
+            off()
+            for key in set(eng._graphs) - base:                # keep the LRU of 8 out of the count
+                del eng._graphs[key]
+
+
 def test_partial_fp32_text_stream_sits_between_the_default_and_the_split_mode():
     """`set_text_stream32_from(k)`: fp32 residual-stream storage for the fusion layers >= k only.  k = 0 IS the split mode (text stream
     fp32, ViT fp16) bit for bit, k = None the default; a k in between lands between the two in distance to the exact mode."""

@@ -1,10 +1,10 @@
 """cir_cross_attention_folded_long without a GPU: the entry point's host-side refusals (fake, never dereferenced device addresses, as
 test_abi.py::test_argument_validation_happens_before_any_launch) and NlvrEngine's choice between the long-caption fold and the projected
-path, with `ops` replaced by recording stubs that return tensors of the right shape."""
-import warnings
-
+path, with `ops` replaced by recording stubs that return tensors of the right shape (tests/engine_stub.py)."""
 import pytest
 import torch
+
+from tests.engine_stub import run_forward
 
 EINVAL, ESHAPE, EALIGN, EDTYPE = -1, -2, -3, -4
 P = 0x10000          # 16-byte aligned fake device address
@@ -56,49 +56,6 @@ def test_short_fold_still_refuses_33_tokens():
 
 
 # ------------------------------------------------------------------------------------------------ engine dispatch
-class _StubOps:
-    """Stands in for candidate_reranking_cir_amd.ops inside engine.forward: every kernel call is recorded and answered with zeros of the
-    shape and type the real call returns."""
-    ACT_GELU, ACT_RELU = 1, 2
-    PROFILE_GEMM = PROFILE_ATTN = None
-
-    def __init__(self):
-        self.calls = []
-
-    def embed_layernorm(self, ids, word, pos, gamma, beta, eps, dtype16=torch.bfloat16, stream_dtype=torch.float32):
-        return torch.zeros(tuple(ids.shape) + (word.shape[1],), dtype=stream_dtype), None
-
-    def gather_rows(self, src, index, dtype):
-        return torch.zeros((src.shape[0] if index is None else index.shape[0], src.shape[1]), dtype=dtype)
-
-    def gemm(self, a, w, bias=None, act=0, residual=None, out=None, out_dtype=None):
-        self.calls.append(("gemm", tuple(a.shape), tuple(w.shape)))
-        return out if out is not None else torch.zeros(tuple(a.shape[:-1]) + (w.shape[-2],), dtype=out_dtype or a.dtype)
-
-    def attention(self, q, k, v, out, scale, mask=None, **kw):
-        self.calls.append(("attention", tuple(q.shape), tuple(k.shape)))
-        return out
-
-    def layernorm(self, x, gamma, beta, eps, residual=None, want32=True, dtype16=None, stream_dtype=torch.float32):
-        nb = max(x.shape[0] if x.dim() == 3 else 1, gamma.shape[0] if gamma.dim() == 2 else 1, residual.shape[0] if residual is not None and residual.dim() == 3 else 1)
-        shape = (nb,) + tuple(x.shape[-2:]) if (x.dim() == 3 or nb > 1) else tuple(x.shape)       # (ops._ln_views' batch broadcast)
-        return (torch.zeros(shape, dtype=stream_dtype) if want32 else None, torch.zeros(shape, dtype=dtype16) if dtype16 is not None else None)
-
-    def cls_cross_attention(self, tok, qp, scale, x_index=None):
-        return torch.zeros((tok.shape[0], 32, tok.shape[2]), dtype=tok.dtype)
-
-    def cross_attention_folded(self, q, x, wkt, wvp, bv, out, l, scale, heads=12, mask=None):
-        self.calls.append(("folded", l, x.shape[1], mask is not None))
-        return out
-
-    def cross_attention_folded_long(self, q, x, wkt, wvp, bv, out, l, scale, heads=12, mask=None):
-        self.calls.append(("folded_long", l, x.shape[1], mask is not None))
-        return out
-
-    def small_linear(self, y, w, b):
-        return torch.zeros((y.shape[0], w.shape[0]), dtype=torch.float32)
-
-
 LAYERS = 4           # fusion layers 0 .. 2 run per-token cross-attention (the full model's 0 .. 10), the last one the CLS rows only; the choice of
                      # path does not look at the layer index, and packing 12 layers on the host takes 8 s
 
@@ -119,17 +76,8 @@ def engine():
 
 
 def _run(engine, monkeypatch, l, n, cand_mask=False):
-    from candidate_reranking_cir_amd import engine as E
-    stub = _StubOps()
-    monkeypatch.setattr(E, "ops", stub)
     q_n, k = 1, 2
-    ids = torch.ones((q_n, l), dtype=torch.int64)
-    cand = torch.zeros((q_n * k, n, D), dtype=torch.float16)
-    cm = torch.ones((q_n * k, n), dtype=torch.int64) if cand_mask else None
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        out = engine.forward(ids, torch.ones_like(ids), torch.zeros((q_n, l, D)), cand, torch.zeros(q_n * k, dtype=torch.int64), cand_mask=cm)
-    assert tuple(out.shape) == (q_n * k, 2)
+    stub, _, w = run_forward(engine, monkeypatch, l, n, q_n, k, cand_mask)
     kv_gemms = [c for c in stub.calls if c[0] == "gemm" and c[1] == (q_n * k * n, D) and c[2] == (4 * D, D)]
     return stub.calls, kv_gemms, [x for x in w if "projected" in str(x.message)]
 
