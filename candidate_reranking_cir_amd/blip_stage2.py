@@ -120,6 +120,8 @@ class _EngineHost(nn.Module):
                                                # everywhere) - `set_text_stream32_from`
         self.long_caption_fold = False         # two-branch encoder: captions of 33-64 tokens take the long-caption query-side fold instead of the
                                                # projected K|V path (`set_long_caption_fold`; off by default)
+        self.short_caption_fold = False        # two-branch encoder: captions of at most 16 tokens take the one-block query-side fold instead of the
+                                               # 32-token kernels (`set_short_caption_fold`; off by default)
         self.graph_candidates = 0              # `score` calls with at most this many candidate rows replay a captured HIP graph per
                                                # shape (0 = off; `enable_graphs`): single-query serving is launch-bound from the host
 
@@ -298,6 +300,7 @@ class BLIP_NLVR(_EngineHost):
                        stream_dtype=self.stream_dtype, cross_dtype=self.token_dtype, split3=self.text_split3 if self.precision == "text32" else 0)
         e.stream32_from = self.text_stream32_from
         e.fold_long = self.long_caption_fold
+        e.fold_short = self.short_caption_fold
         return e
 
     def set_long_caption_fold(self, on: bool = True):
@@ -308,6 +311,17 @@ class BLIP_NLVR(_EngineHost):
         self.long_caption_fold = bool(on)
         if self._engines is not None:
             self._engines[1].fold_long = self.long_caption_fold
+        return self
+
+    def set_short_caption_fold(self, on: bool = True):
+        """Captions of at most 16 tokens (the reference never pads a query: batch 1, padding='longest', blip_stage2.py:113; CIRR and FashionIQ
+        modification sentences are short) against up to 608 image tokens: run the cross-attention of fusion layers 0-10 through
+        cir_cross_attention_folded_short - one 16-token block per head - instead of the 32-token kernels, which compute a second block on zero
+        queries.  Off by default: it measures faster at 225-608 image tokens (384 px) and slower at up to 224 (LABNOTES.md section 18).  The setting lives on the model and is re-applied to every
+        engine packed from it."""
+        self.short_caption_fold = bool(on)
+        if self._engines is not None:
+            self._engines[1].fold_short = self.short_caption_fold
         return self
 
     def _vit_engine(self, sd) -> VitEngine:

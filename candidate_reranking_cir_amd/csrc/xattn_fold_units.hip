@@ -1,12 +1,14 @@
-// The query-side fold of xattn_fold.hip in 16-row steps: one kernel body, X staged per 32-feature UNIT, behind two entry points -
+// The query-side fold of xattn_fold.hip in 16-row steps: one kernel body, X staged per 32-feature UNIT, behind three entry points -
 //   cir_cross_attention_folded for 225 .. 608 image tokens (the reference's 384-px geometry: 577 tokens; validate_stage2.py:327), L <= 32;
 //   cir_cross_attention_folded_long for captions of up to 64 tokens against up to 224 image tokens (nlvr_encoder.py:150-168, 183-217 with
 //   encoder_hidden_states = the candidate's image tokens; the reference tokenises with padding='longest' and no 32-token cut,
-//   blip_stage2.py:113, and FashionIQ joins two captions per query).
+//   blip_stage2.py:113, and FashionIQ joins two captions per query);
+//   cir_cross_attention_folded_short for captions of at most 16 tokens against up to 608 image tokens: one 16-row block per head and no more.
 // The work is 12 ceil(L / 16) 16-row blocks per (candidate, branch) and nothing more: a wave owns ONE head and NB consecutive 16-token blocks of
 // it, which share every X fragment read from LDS and every W_k^T / W_v fragment of their head.  The transposed score tile S^T of a block
 // against KB 16-key blocks is KB accumulator tiles = 4 KB registers, and that decides the instantiations:
 //     608 keys (KB = 38), L <= 32: NB = 1, two waves per head (S^T = 152 registers; three blocks, as in the 224-key kernel, would need 456)
+//                         L <= 16: NB = 1, one wave per head (cir_cross_attention_folded_short only)
 //     224 keys (KB = 14), L <= 16: NB = 1, one wave per head      L <= 32: NB = 2, one wave per head
 //                         L <= 48: NB = 3, one wave per head (S^T = 168 registers)      L <= 64: NB = 2, two waves per head (S^T = 112 registers)
 // A workgroup covers 4 heads (4 or 8 waves); three workgroups per (candidate, branch), none waits for another: 4 heads x 32 tokens = 128 stacked
@@ -310,8 +312,8 @@ __device__ __forceinline__ void fold_unit_body(const FoldArgs& a) {
     }
 }
 
-// Three kernels around the one body, two waves per SIMD each (256 registers): 608 keys, two waves of one block per head (8 waves); 224 keys,
-// one wave of NB blocks per head (4 waves); 224 keys, two waves of two blocks per head (8 waves).
+// Four kernels around the one body, two waves per SIMD each (256 registers): 608 keys, two waves of one block per head (8 waves); 224 keys,
+// one wave of NB blocks per head (4 waves); 224 keys, two waves of two blocks per head (8 waves); 608 keys, one wave of one block per head (4 waves).
 // (separate kernels with literal bounds: a launch bound that depends on a template parameter, 256 * WPH, fails to substitute in hipcc's host pass)
 template <typename T, bool MASKED>
 __global__ __launch_bounds__(512, 2) void xattn_fold16_kernel(const FoldArgs a) { fold_unit_body<T, MASKED, 1, 2, 38>(a); }
@@ -319,6 +321,12 @@ template <typename T, bool MASKED, int NB>
 __global__ __launch_bounds__(256, 2) void xattn_fold_long_kernel(const FoldArgs a) { fold_unit_body<T, MASKED, NB, 1, kFoldKB>(a); }
 template <typename T, bool MASKED>
 __global__ __launch_bounds__(512, 2) void xattn_fold_long64_kernel(const FoldArgs a) { fold_unit_body<T, MASKED, 2, 2, kFoldKB>(a); }
+// 608 keys, captions of at most 16 tokens: one wave of one block per head (4 waves) - fold16 without its second, all-zero wave.  10 phase-1 and
+// 15 phase-2 DMA pieces per wave (40 for 38 key blocks, 60 for 57 KiB): the surplus pieces lie inside the unit buffer and read rows clamped to
+// N - 1, and the 14 (19) memory requests of a unit spread over its 38 key-block steps.  128.5 KiB of LDS: one workgroup per CU whatever the
+// bound; (256, 2) keeps S^T in 234 VGPRs, (256, 1) moves it to AGPRs and pays ~400 v_accvgpr copies (LABNOTES.md section 18).
+template <typename T, bool MASKED>
+__global__ __launch_bounds__(256, 2) void xattn_fold16_short_kernel(const FoldArgs a) { fold_unit_body<T, MASKED, 1, 1, 38>(a); }
 
 template <int NB, int WPH, int KB>
 static int launch_fold_units(FoldKernel kernel, const FoldArgs& a, hipStream_t s) {
@@ -342,6 +350,13 @@ static int launch_fold_long(const FoldArgs& a, hipStream_t s) {
     return launch_fold_units<2, 2, kFoldKB>(xattn_fold_long64_kernel<T, MASKED>, a, s);
 }
 
+// captions of at most 16 tokens: 12 blocks per (candidate, branch) at either key count
+template <typename T, bool MASKED>
+static int launch_fold_short(const FoldArgs& a, hipStream_t s) {
+    if (a.N <= 16 * kFoldKB) return launch_fold_units<1, 1, kFoldKB>(xattn_fold_long_kernel<T, MASKED, 1>, a, s);
+    return launch_fold_units<1, 1, 38>(xattn_fold16_short_kernel<T, MASKED>, a, s);
+}
+
 }  // namespace cir
 
 // The query-side fold for captions of up to 64 tokens (nlvr_encoder.py:150-168, 183-217; blip_stage2.py:113: padding='longest', no
@@ -357,4 +372,19 @@ extern "C" int cir_cross_attention_folded_long(const void* q, int64_t q_sb, int6
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == CIR_BF16) return key_mask ? launch_fold_long<__bf16, true>(a, s) : launch_fold_long<__bf16, false>(a, s);
     return key_mask ? launch_fold_long<_Float16, true>(a, s) : launch_fold_long<_Float16, false>(a, s);
+}
+
+// The query-side fold for captions of at most 16 tokens (nlvr_encoder.py:150-168, 183-217; blip_stage2.py:113: batch 1, padding='longest' -
+// a short modification sentence is never padded to 32) against up to 608 keys; parameters as cir_cross_attention_folded.
+extern "C" int cir_cross_attention_folded_short(const void* q, int64_t q_sb, int64_t q_rs, const void* x, int64_t x_s1, const void* wkt, const void* wvp,
+                                                int64_t w_sb, const float* bv, const float* key_mask, int64_t mask_stride, void* out, int64_t o_st,
+                                                int64_t o_sr, int64_t o_sb, int T, int L, int N, int D, int H, float scale, int dtype, void* stream) {
+    using namespace cir;
+    FoldArgs a;
+    const int rc = fold_args(a, q, q_sb, q_rs, x, x_s1, wkt, wvp, w_sb, bv, key_mask, mask_stride, out, o_st, o_sr, o_sb, T, L, N, D, H, scale, dtype,
+                             16, 608, (int64_t)T * 6 + 8);
+    if (rc != CIR_OK) return rc;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == CIR_BF16) return key_mask ? launch_fold_short<__bf16, true>(a, s) : launch_fold_short<__bf16, false>(a, s);
+    return key_mask ? launch_fold_short<_Float16, true>(a, s) : launch_fold_short<_Float16, false>(a, s);
 }

@@ -314,7 +314,7 @@ class MedEngine:
 class LayerPlan(NamedTuple):
     """One fusion layer of a `Plan`."""
     cls_only: bool          # per-token work on the CLS rows only (the trimmed last layer)
-    cross: str              # cross-attention path: "cls_fold", "fold32", "fold_long", "projected" or "bank"
+    cross: str              # cross-attention path: "cls_fold", "fold_short", "fold32", "fold_long", "projected" or "bank"
     sdt: torch.dtype        # residual-stream type the layer receives ...
     sdt_out: torch.dtype    # ... and the one its last LayerNorm writes (the next layer's)
 
@@ -342,7 +342,7 @@ class NlvrEngine:
     Layer 0's self-attention block is candidate-independent and runs once per QUERY.
 
     Which of these launches a call issues is decided in one place: `plan` maps the call's sizes and the live switches (plain attributes,
-    set between calls: `trim_last`, `kv_chunk`, `fold_cls_kv`, `fold_cross_kv`, `fold_long`, `stream32_from`, `cls_fold`) to a `Plan` before
+    set between calls: `trim_last`, `kv_chunk`, `fold_cls_kv`, `fold_cross_kv`, `fold_long`, `fold_short`, `stream32_from`, `cls_fold`) to a `Plan` before
     the first launch; `forward` executes it and `forward_graphed` keys its captures with it.  A new host-side switch belongs in `plan`.
     """
 
@@ -369,6 +369,11 @@ class NlvrEngine:
         # it measures faster than the projected path at 33-48 tokens and slower at 49-64 (LABNOTES.md section 14); a default per length is a later
         # change (BLIP_NLVR.set_long_caption_fold).
         self.fold_long = False
+        # Captions of at most 16 tokens: with `fold_short` on they take cir_cross_attention_folded_short (one 16-token block per head: 12 blocks
+        # per candidate and branch where the 32-token kernels run 24) at up to 608 keys.  Off by default: per layer it measures 7-8 % faster than
+        # fold16 at 577 keys and 19-28 % slower than the 224-key kernel at 197 (LABNOTES.md section 18) - worth turning on for 384-px runs only
+        # (BLIP_NLVR.set_short_caption_fold).
+        self.fold_short = False
         self.stream32_from = None    # layers >= this index keep their residual stream in fp32 (None: `stream_dtype` everywhere)
         self._graphs = {}            # graph_key -> ScoreGraph, in recency order (`forward_graphed`)
         e = prefix + "embeddings."
@@ -458,6 +463,8 @@ class NlvrEngine:
                 cross = "cls_fold"
             elif no_kv:
                 raise ValueError("this K/V bank was built with the last layer folded (no K|V of that layer): rebuild it with fold_cls_kv = False")
+            elif foldable and self.fold_short and l <= 16 and n <= 608:
+                cross = "fold_short"
             elif foldable and l <= 32 and n <= 608:
                 cross = "fold32"
             elif foldable and self.fold_long and 33 <= l <= 64 and n <= 224:
@@ -557,8 +564,8 @@ class NlvrEngine:
         emask = None if emask2d is None else emask2d.view(t_n, 1, n).expand(t_n, 2, n)
         if lp.cross == "cls_fold":
             self._cross_cls_fold(qc, ccl, tok, rows)
-        elif lp.cross in ("fold32", "fold_long"):
-            fold = ops.cross_attention_folded if lp.cross == "fold32" else ops.cross_attention_folded_long
+        elif lp.cross in ("fold_short", "fold32", "fold_long"):
+            fold = getattr(ops, {"fold_short": "cross_attention_folded_short", "fold32": "cross_attention_folded", "fold_long": "cross_attention_folded_long"}[lp.cross])
             fold(qraw, tok, ly["wkt"], ly["wvp"], ly["bvf"], ccl, l, SCALE, heads=self.geo.num_attention_heads, mask=emask2d)
         elif lp.cross == "projected":
             self._cross_projected(ly, qc, ccl, tok, emask, kv_chunk)

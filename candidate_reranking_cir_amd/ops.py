@@ -485,7 +485,7 @@ def fold_pack_value(wv: torch.Tensor) -> torch.Tensor:
 
 def _cross_attention_folded(entry: str, q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, wvp: torch.Tensor, bv: torch.Tensor, out: torch.Tensor, l: int,
                             scale: float, heads: int, mask: Optional[torch.Tensor]) -> torch.Tensor:
-    """The marshalling and the PROFILE_ATTN record that the two folded entry points share (same parameter list, include/cirrank.h)."""
+    """The marshalling and the PROFILE_ATTN record that the folded entry points share (same parameter list, include/cirrank.h)."""
     _need_cuda(q, x, wkt, wvp, bv, out)
     t_n, n, d = x.shape
     assert q.shape == (2, t_n * l, d) and q.stride(2) == 1 and x.stride(2) == 1 and x.stride(1) == d
@@ -518,6 +518,13 @@ def cross_attention_folded_long(q: torch.Tensor, x: torch.Tensor, wkt: torch.Ten
     """cross_attention_folded for captions of up to 64 tokens against up to 224 keys (cir_cross_attention_folded_long): the same operands and
     packed weights; the cost grows with the caption in 16-token steps."""
     return _cross_attention_folded("cir_cross_attention_folded_long", q, x, wkt, wvp, bv, out, l, scale, heads, mask)
+
+
+def cross_attention_folded_short(q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, wvp: torch.Tensor, bv: torch.Tensor, out: torch.Tensor, l: int,
+                                 scale: float, heads: int = 12, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cross_attention_folded for captions of at most 16 tokens against up to 608 keys (cir_cross_attention_folded_short): the same operands
+    and packed weights; one 16-token block per head instead of two."""
+    return _cross_attention_folded("cir_cross_attention_folded_short", q, x, wkt, wvp, bv, out, l, scale, heads, mask)
 
 
 def embed_layernorm(ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,

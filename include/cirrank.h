@@ -256,6 +256,18 @@ int cir_cross_attention_folded_long(const void* q, int64_t q_sb, int64_t q_rs, c
                                     int T, int L, int N, int D, int H, float scale, int dtype, void* stream);
 
 /*
+ * cir_cross_attention_folded for captions of at most 16 tokens (csrc/xattn_fold_units.hip; additive within ABI v15): the same operator
+ * (nlvr_encoder.py:150-168, 183-217), the same operands, packed weights, key mask and strides, for the short modification sentences the reference
+ * never pads (blip_stage2.py:113: batch 1, padding='longest').  D = 768, H = 12, L <= 16, N <= 608 (CIR_ESHAPE otherwise: use
+ * cir_cross_attention_folded).  One wave per head and one 16-token block: 12 blocks per candidate and branch where cir_cross_attention_folded
+ * runs 24 (N <= 224: its 32 stacked rows per head group; 225 .. 608: a second wave per head on zero queries).  A row's bits are those of
+ * cir_cross_attention_folded at 225 .. 608 keys and of cir_cross_attention_folded_long at <= 224 keys (same body, same accumulation order).
+ */
+int cir_cross_attention_folded_short(const void* q, int64_t q_sb, int64_t q_rs, const void* x, int64_t x_s1, const void* wkt, const void* wvp, int64_t w_sb,
+                                     const float* bv, const float* key_mask, int64_t mask_stride, void* out, int64_t o_st, int64_t o_sr, int64_t o_sb,
+                                     int T, int L, int N, int D, int H, float scale, int dtype, void* stream);
+
+/*
  * BertEmbeddings.forward (nlvr_encoder.py:68-91, med.py:87-110):
  *   y[r] = LayerNorm(word[ids[r]] + pos[r % L]) for r < rows; fp32 tables, outputs as cir_layernorm
  *   (y_stream in CIR_F32 / CIR_F16, y16 in dtype16).

@@ -1,16 +1,21 @@
 """Long-caption query-side fold (cir_cross_attention_folded_long, 33-64 caption tokens) against the projected path (K|V GEMM + cir_attention)
-on the same tensors.  GPU box only.
+on the same tensors; with `--fold short`, the one-block fold for captions of at most 16 tokens (cir_cross_attention_folded_short) against the
+32-token kernels (cir_cross_attention_folded) on the same tensors.  GPU box only.
 
   python tools/fold_long_bench.py                       one fusion layer: L in {33, 40, 48, 49, 64}, N = 197, T = 6720, fp16 and bf16
   python tools/fold_long_bench.py --mode step --tokens 40
                                                         a whole scoring step (64 queries x 105 candidates, 224 px: ViT, stage-I z_t, fusion) with
                                                         BLIP_NLVR.set_long_caption_fold on and off
-  options: --t T  --n N  --lengths 33,40,..  --dtypes fp16,bf16  --rounds R  --json out.json
+  python tools/fold_long_bench.py --fold short          one fusion layer: L in {8, 12, 16} at (N, T) = (197, 6720) and (577, 1680), fp16 and bf16
+  python tools/fold_long_bench.py --fold short --mode step --tokens 12 [--px 384 --queries 16]
+                                                        the scoring step with BLIP_NLVR.set_short_caption_fold on and off
+  options: --t T  --n N  --lengths 33,40,..  --dtypes fp16,bf16  --rounds R  --px 224|384  --json out.json
 
 Method: every shape is launched before it is timed and the part is warmed for 1.5 s on the work it is about to time; the two forms ALTERNATE
 inside a round (device events around `inner` back-to-back launches each), and the figure is the MEDIAN over the rounds, with the spread
 (min .. max) beside it.  Flops are the ones each form executes, computed from the shapes: the fold 2 T (2 H Lp 64 D + 2 H Lp D Np) with
-Lp = 16 ceil(L / 16) rows and Np = 224 keys as the kernel runs them, the projected path 2 T N D 4 D + 4 T 2 L N D."""
+Lp = 16 ceil(L / 16) rows and Np = 224 keys as the kernel runs them, the projected path 2 T N D 4 D + 4 T 2 L N D; with `--fold short` both
+forms are folds: Lp = 16 rows against 32, Np = 224 keys up to 224 and 608 above."""
 import argparse
 import json
 import os
@@ -99,16 +104,48 @@ def layer_mode(a):
     return dict(mode="layer", rounds=a.rounds, inner=a.inner, rows=rows)
 
 
+def short_layer_mode(a):
+    """cir_cross_attention_folded_short against cir_cross_attention_folded (the path the engine takes with the switch off) on the same tensors."""
+    rows = []
+    shapes = [(a.n, a.t)] if a.n or a.t else [(197, 6720), (577, 1680)]
+    for dname in a.dtypes.split(","):
+        dt = {"fp16": torch.float16, "bf16": torch.bfloat16}[dname]
+        g = torch.Generator(device="cuda").manual_seed(0)
+        r = lambda shape, s: (torch.randn(shape, generator=g, device="cuda") * s).to(dt)
+        wkt, wvp, bv = ops.fold_pack_key(r((2, D, D), 0.03)), ops.fold_pack_value(r((2, D, D), 0.03)), torch.randn((2, D), device="cuda") * 0.5
+        for n, t_n in shapes:
+            n, t_n = n or 197, t_n or 6720
+            x = r((t_n, n, D), 1.0)
+            for l in [int(s) for s in (a.lengths or "8,12,16").split(",")]:
+                q = r((2, t_n * l, D), 1.0)
+                out, o2 = (torch.empty((t_n, l, 2, D), dtype=dt, device="cuda") for _ in range(2))
+                ms = _alternate({"short": lambda: ops.cross_attention_folded_short(q, x, wkt, wvp, bv, out, l, 0.125),
+                                 "fold32": lambda: ops.cross_attention_folded(q, x, wkt, wvp, bv, o2, l, 0.125)}, a.rounds, a.inner)
+                (ts, ts0, ts1), (tp, tp0, tp1) = _stat(ms["short"]), _stat(ms["fold32"])
+                np_ = 224 if n <= 224 else 608
+                fl = lambda lp: 2.0 * t_n * 2 * (2 * H * lp * 64 * D + 2 * H * lp * D * np_)
+                diff = (out.float() - o2.float()).abs().max().item()
+                print(f"{dname} T {t_n} L {l} N {n}: folded_short {ts * 1e3:.0f} us [{ts0 * 1e3:.0f} .. {ts1 * 1e3:.0f}] ({fl(16) / ts / 1e9:.0f} TFLOP/s executed)   "
+                      f"folded {tp * 1e3:.0f} us [{tp0 * 1e3:.0f} .. {tp1 * 1e3:.0f}] ({fl(32) / tp / 1e9:.0f} TFLOP/s executed)   ratio {ts / tp:.3f}   "
+                      f"max|short - folded| {diff:.2e}", flush=True)
+                rows.append(dict(dtype=dname, T=t_n, L=l, N=n, folded_short_us=round(ts * 1e3, 1), folded_short_us_min_max=[round(ts0 * 1e3, 1), round(ts1 * 1e3, 1)],
+                                 folded_us=round(tp * 1e3, 1), folded_us_min_max=[round(tp0 * 1e3, 1), round(tp1 * 1e3, 1)], ratio=round(ts / tp, 4),
+                                 folded_short_tflops=round(fl(16) / ts / 1e9, 1), folded_tflops=round(fl(32) / tp / 1e9, 1), max_abs_diff=diff))
+                del q, out, o2
+            del x
+    return dict(mode="layer", fold="short", rounds=a.rounds, inner=a.inner, rows=rows)
+
+
 def step_mode(a):
     from candidate_reranking_cir_amd import config, synthetic
     from candidate_reranking_cir_amd.blip_stage1 import BLIP_Retrieval
     from candidate_reranking_cir_amd.blip_stage2 import BLIP_NLVR
     q_n, k, l = a.queries, a.k, a.tokens
     dev = torch.device("cuda")
-    g, v = config.BertGeometry(), config.VitGeometry(image_size=224)
+    g, v = config.BertGeometry(), config.VitGeometry(image_size=a.px)
     m2 = BLIP_NLVR(med_config=g, vit_geometry=v, tokenizer=synthetic.HashTokenizer()).to(dev).eval()
     m1 = BLIP_Retrieval(med_config=g, vit_geometry=v, tokenizer=synthetic.HashTokenizer()).to(dev).eval()
-    images = torch.randn((q_n + q_n * k, 3, 224, 224), device=dev).half()
+    images = torch.randn((q_n + q_n * k, 3, a.px, a.px), device=dev).half()
     ids = torch.stack([synthetic.caption_ids(q, l) for q in range(q_n)]).to(dev)
     mask = torch.ones_like(ids)
     qidx = torch.arange(q_n, device=dev).repeat_interleave(k)
@@ -121,40 +158,49 @@ def step_mode(a):
     import warnings
     warnings.simplefilter("ignore")                             # (the switch-off form reports its projected path once)
 
+    switch = m2.set_long_caption_fold if a.fold == "long" else m2.set_short_caption_fold
+
     def form(on):
         def run():
-            m2.set_long_caption_fold(on)
+            switch(on)
             return step()
         return run
 
-    ms = _alternate({"fold_long_on": form(True), "fold_long_off": form(False)}, a.rounds, 1, warm_s=3.0)
-    m2.set_long_caption_fold(True); lon = step()
-    m2.set_long_caption_fold(False); loff = step()
-    (t1, a1, b1), (t0, a0, b0) = _stat(ms["fold_long_on"]), _stat(ms["fold_long_off"])
+    name = f"fold_{a.fold}"
+    ms = _alternate({name + "_on": form(True), name + "_off": form(False)}, a.rounds, 1, warm_s=3.0)
+    switch(True); lon = step()
+    switch(False); loff = step()
+    (t1, a1, b1), (t0, a0, b0) = _stat(ms[name + "_on"]), _stat(ms[name + "_off"])
     diff = (lon - loff).abs().max().item()
-    print(f"step {q_n} x {k}, {l} caption tokens, 224 px: switch on {t1:.1f} ms [{a1:.1f} .. {b1:.1f}]   off {t0:.1f} ms [{a0:.1f} .. {b0:.1f}]   "
+    print(f"step {q_n} x {k}, {l} caption tokens, {a.px} px, {name}: switch on {t1:.1f} ms [{a1:.1f} .. {b1:.1f}]   off {t0:.1f} ms [{a0:.1f} .. {b0:.1f}]   "
           f"ratio {t1 / t0:.3f}   fold_fallbacks {m2.engines()[1].fold_fallbacks}   max|logit difference| {diff:.2e}", flush=True)
-    return dict(mode="step", queries=q_n, k=k, tokens=l, rounds=a.rounds, on_ms=round(t1, 2), on_ms_min_max=[round(a1, 2), round(b1, 2)],
+    return dict(mode="step", fold=a.fold, px=a.px, queries=q_n, k=k, tokens=l, rounds=a.rounds, on_ms=round(t1, 2), on_ms_min_max=[round(a1, 2), round(b1, 2)],
                 off_ms=round(t0, 2), off_ms_min_max=[round(a0, 2), round(b0, 2)], ratio=round(t1 / t0, 4), max_abs_logit_diff=diff)
 
 
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--mode", choices=["layer", "step"], default="layer")
-    p.add_argument("--t", type=int, default=6720)
-    p.add_argument("--n", type=int, default=197)
-    p.add_argument("--lengths", default="33,40,48,49,64")
+    p.add_argument("--fold", choices=["long", "short"], default="long")
+    p.add_argument("--px", type=int, choices=[224, 384], default=224)
+    p.add_argument("--t", type=int, default=None)
+    p.add_argument("--n", type=int, default=None)
+    p.add_argument("--lengths", default=None)
     p.add_argument("--dtypes", default="fp16,bf16")
     p.add_argument("--rounds", type=int, default=7)
     p.add_argument("--inner", type=int, default=5)
-    p.add_argument("--tokens", type=int, default=40)
+    p.add_argument("--tokens", type=int, default=None)
     p.add_argument("--queries", type=int, default=64)
     p.add_argument("--k", type=int, default=105)
     p.add_argument("--json", default=None)
     args = p.parse_args()
     if not torch.cuda.is_available():
         sys.exit("fold_long_bench.py measures on an MI355X: no GPU found")
-    res = layer_mode(args) if args.mode == "layer" else step_mode(args)
+    if args.tokens is None:
+        args.tokens = 40 if args.fold == "long" else 12
+    if args.fold == "long":
+        args.t, args.n, args.lengths = args.t or 6720, args.n or 197, args.lengths or "33,40,48,49,64"
+    res = step_mode(args) if args.mode == "step" else layer_mode(args) if args.fold == "long" else short_layer_mode(args)
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
         with open(args.json, "w") as f:
