@@ -15,14 +15,41 @@ import numpy as np
 import torch
 
 from . import ops
-from .validate_stage2 import RelativeValSet, generate_val_predictions
+from .validate_stage2 import RelativeValSet, _bank16, generate_val_predictions, relative_test_set_from_dataset
+
+
+def generate_cirr_test_dicts(*args, **kw) -> Tuple[Dict[str, List[str]], Dict[str, List[str]]]:
+    """Top-50 global and top-3 subset predictions per pair id (cirr_test_submission_stage2.py:74-108).  Two call forms.  Native:
+    (blip_model, model_stage1, RelativeValSet, index_features, index_names, pair_ids, query_batch=8, kv_bank=None) - `ds.labels` is
+    ignored: all queries are scored; `ds.group_index` holds the 5 non-reference members.  The reference's own (:74-78):
+    (relative_test_dataset, blip_model, model_stage1, index_features, index_names, query_batch=..., kv_bank=...) over 5-field test items
+    (data_utils.py:346) and the fp32 `index_features` of utils.py:43-55; it runs the native form underneath."""
+    third = args[2] if len(args) > 2 else kw.get("ds")
+    if isinstance(third, RelativeValSet):
+        return _cirr_test_dicts(*args, **kw)
+    names = ("relative_test_dataset", "blip_model", "model_stage1", "index_features", "index_names")
+    if len(args) > len(names):
+        raise TypeError("reference form: (relative_test_dataset, blip_model, model_stage1, index_features, index_names)")
+    relative_test_dataset, blip_model, model_stage1, index_features, index_names = list(args) + [kw.pop(n) for n in names[len(args):]]
+    ds, _, _, pair_ids = relative_test_set_from_dataset(relative_test_dataset, index_names)
+    return _cirr_test_dicts(blip_model, model_stage1, ds, _bank16(blip_model, index_features), list(index_names), pair_ids, **kw)
+
+
+def generate_cirr_test_predictions(blip_model, model_stage1, relative_test_dataset, index_names: Sequence[str], index_features: torch.Tensor, **kw):
+    """cirr_test_submission_stage2.py:111-178 in the reference's call form, over 5-field test items (data_utils.py:346):
+    (predicted_logits (Q, K), group_predicted_logits (Q, 5), reference_names, group_members_noRef, pairs_id) - the batched loop
+    underneath (`query_batch=`, `kv_bank=`), every query scored."""
+    if isinstance(index_names, torch.Tensor) or not isinstance(index_features, torch.Tensor):
+        raise TypeError("reference form takes index_names (list of str) BEFORE index_features (tensor), cirr_test_submission_stage2.py:111-113")
+    ds, refs, members, pair_ids = relative_test_set_from_dataset(relative_test_dataset, index_names)
+    logits, glogits = generate_val_predictions(blip_model, model_stage1, ds, _bank16(blip_model, index_features), **kw)
+    return logits, glogits, refs, members, pair_ids
 
 
 @torch.no_grad()
-def generate_cirr_test_dicts(blip_model, model_stage1, ds: RelativeValSet, index_features: torch.Tensor, index_names: Sequence[str],
-                             pair_ids: Sequence[int], query_batch: int = 8, kv_bank=None) -> Tuple[Dict[str, List[str]], Dict[str, List[str]]]:
-    """Top-50 global and top-3 subset predictions per pair id (cirr_test_submission_stage2.py:74-108).
-    `ds.labels` is ignored: all queries are scored; `ds.group_index` holds the 5 non-reference members."""
+def _cirr_test_dicts(blip_model, model_stage1, ds: RelativeValSet, index_features: torch.Tensor, index_names: Sequence[str],
+                     pair_ids: Sequence[int], query_batch: int = 8, kv_bank=None) -> Tuple[Dict[str, List[str]], Dict[str, List[str]]]:
+    """The native form of `generate_cirr_test_dicts`."""
     all_true = RelativeValSet(ref_index=ds.ref_index, cand_index=ds.cand_index, labels=np.ones_like(ds.cand_index, dtype=bool),
                               captions=ds.captions, input_ids=ds.input_ids, attention_mask=ds.attention_mask,
                               group_index=ds.group_index, target_index=ds.target_index)

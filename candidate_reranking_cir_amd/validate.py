@@ -10,6 +10,7 @@ read back at data_utils.py:166-179, 290-305): `sorted_index_names (Q,K) str`, `t
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -17,7 +18,7 @@ import torch
 
 from . import ops
 from .blip_stage2 import encode_text
-from .validate_stage2 import RelativeValSet
+from .validate_stage2 import RelativeValSet, _bank16, fiq_caption
 
 
 @torch.no_grad()
@@ -174,16 +175,224 @@ def save_topk(path: str, top: dict) -> None:
 
 
 def load_topk(path: str, k: int, ref_index: np.ndarray, captions: Optional[List[str]] = None,
-              group_index: Optional[np.ndarray] = None, target_index: Optional[np.ndarray] = None) -> RelativeValSet:
+              group_index: Optional[np.ndarray] = None, target_index: Optional[np.ndarray] = None, split: Optional[str] = None) -> RelativeValSet:
     """Read a top-K file (ours or the authors') into the tensor form stage II consumes: names -> rows of `index_names`
-    (data_utils.py:166-179, 290-305 keep the first K columns the same way)."""
+    (data_utils.py:166-179, 290-305 keep the first K columns the same way).  A file without `labels` / `target_names` - the test1 schema,
+    cirr_test_submission.py:121-127, which data_utils.py:299 reads without them - gives all-true labels (every query is scored) and no
+    `target_index` unless the caller passes one.  `split`, where given, must be the file's (data_utils.py:171, 294)."""
     f = torch.load(path, weights_only=False)
     assert k <= f["sorted_index_names"].shape[-1]                           # data_utils.py:169, 293
+    if split is not None and f["split"] != split:
+        raise ValueError(f"{path} holds the top-K of split {f['split']!r}, not {split!r}")
     row_of = {n: i for i, n in enumerate(f["index_names"])}
     names = np.asarray(f["sorted_index_names"])[:, :k]
     cand = np.vectorize(row_of.__getitem__, otypes=[np.int64])(names)
-    labels = np.asarray(f["labels"])[:, :k].astype(bool)
-    if target_index is None:
+    if "labels" in f:
+        labels = np.asarray(f["labels"])[:, :k].astype(bool)
+    else:
+        labels = np.ones(cand.shape, dtype=bool)
+    if target_index is None and "target_names" in f:
         target_index = np.array([row_of[n] for n in f["target_names"]], dtype=np.int64)
     return RelativeValSet(ref_index=np.asarray(ref_index), cand_index=cand, labels=labels, captions=captions,
                           group_index=group_index, target_index=target_index)
+
+
+# ------------------------------------------------------------------------------------------------ reference signatures
+@dataclass
+class RelativeQueries:
+    """A stage-I 'relative' split (no top-K file) in tensor form: every name an integer row of `index_names`, next to the lists of
+    names the reference's generate_* functions return."""
+    ref_index: np.ndarray                      # (Q,)
+    captions: List[str]                        # one per query (FashionIQ: already joined)
+    reference_names: List[str]
+    target_index: Optional[np.ndarray] = None  # (Q,)   val items
+    target_names: Optional[List[str]] = None
+    group_index: Optional[np.ndarray] = None   # (Q, 5) CIRR subset members without the reference
+    group_members: Optional[List[List[str]]] = None   # the 6 members as the dataset holds them, reference included
+    pair_ids: Optional[list] = None            # CIRR test items
+
+    def __len__(self) -> int:
+        return len(self.ref_index)
+
+
+_LAYOUTS = {
+    "fiq_val": (3, "(reference, target, [cap1, cap2]) (FashionIQ val, data_utils.py:212)"),
+    "cirr_val": (4, "(reference, target_hard, caption, 6 group members incl. the reference) (CIRR val, data_utils.py:340)"),
+    "cirr_test": (4, "(pair_id, reference, caption, 6 group members incl. the reference) (CIRR test1, data_utils.py:350)"),
+}
+
+
+def name_rows(index_names: Sequence[str]) -> dict:
+    """name -> row of `index_names`; duplicates raise ValueError (the reference's dict(zip(index_names, index_features)),
+    validate.py:121, would silently keep the last)."""
+    row = {str(n): i for i, n in enumerate(index_names)}
+    if len(row) != len(index_names):
+        raise ValueError("index_names holds duplicates")
+    return row
+
+
+def group_rows(row: dict, reference: str, members) -> List[int]:
+    """Rows of the 5 subset members besides the reference, in the dataset's order (validate.py:219-220 masks them out of rankings
+    that no longer hold the reference; cirr_test_submission_stage2.py:166, 173 drop it the same way)."""
+    rest = [row[str(m)] for m in members if str(m) != str(reference)]
+    if len(members) != 6 or len(rest) != 5:
+        raise ValueError(f"a CIRR subset has 6 members, the reference among them: got {len(members)} members, {len(rest)} besides {reference!r}")
+    return rest
+
+
+def relative_queries_from_dataset(relative_dataset, index_names: Sequence[str], layout: str) -> RelativeQueries:
+    """The reference's stage-I 'relative' dataset (anything with `__len__` and items in one of `_LAYOUTS`) -> RelativeQueries.  Names
+    become rows of `index_names` ONCE here (the reference looks each up in a dict per batch, validate.py:142, 307): a name that is
+    not in the index raises KeyError as there, any other field count TypeError."""
+    fields, text = _LAYOUTS[layout]
+    row = name_rows(index_names)
+    n_q = len(relative_dataset)
+    q = RelativeQueries(ref_index=np.empty(n_q, dtype=np.int64), captions=[], reference_names=[])
+    if layout != "cirr_test":
+        q.target_index, q.target_names = np.empty(n_q, dtype=np.int64), []
+    else:
+        q.pair_ids = []
+    if layout != "fiq_val":
+        q.group_index, q.group_members = np.empty((n_q, 5), dtype=np.int64), []
+    for i in range(n_q):
+        item = relative_dataset[i]
+        if not isinstance(item, (tuple, list)) or len(item) != fields:
+            raise TypeError(f"a stage-I item is {text}; got {len(item) if isinstance(item, (tuple, list)) else type(item).__name__} fields "
+                            "(a dataset built with load_topk= / K= belongs to stage II)")
+        if layout == "fiq_val":
+            ref, tgt, cap = item
+            q.captions.append(fiq_caption(str(cap[0]), str(cap[1])))                        # validate.py:130-133
+        elif layout == "cirr_val":
+            ref, tgt, cap, members = item
+        else:
+            pair_id, ref, cap, members = item
+            q.pair_ids.append(pair_id)
+        ref = str(ref)
+        q.ref_index[i] = row[ref]
+        q.reference_names.append(ref)
+        if layout != "cirr_test":
+            q.target_index[i] = row[str(tgt)]
+            q.target_names.append(str(tgt))
+        if layout != "fiq_val":
+            q.captions.append(str(cap))
+            q.group_index[i] = group_rows(row, ref, members)
+            q.group_members.append([str(m) for m in members])
+    return q
+
+
+def _query_features(blip_model, q: RelativeQueries, index_features: torch.Tensor) -> torch.Tensor:
+    return generate_val_predictions(blip_model, q.ref_index, q.captions, _bank16(blip_model, index_features))
+
+
+def generate_fiq_val_predictions(blip_model, relative_val_dataset, index_names: Sequence[str], index_features: torch.Tensor):
+    """validate.py:102-149 in the reference's call form: (predicted (Q, 256) fp32 on the device, target_names).  `index_features` is
+    what utils.py:57-72 hands over - fp32 (n, N, D) tokens - or the 16-bit bank (one conversion launch otherwise); the features are the
+    native `generate_val_predictions` on the same rows and captions, in batches of 32 padded to the longest caption (:116)."""
+    q = relative_queries_from_dataset(relative_val_dataset, index_names, "fiq_val")
+    return _query_features(blip_model, q, index_features), q.target_names
+
+
+def generate_cirr_val_predictions(blip_model, relative_val_dataset, index_names: Sequence[str], index_features: torch.Tensor):
+    """validate.py:271-316 in the reference's call form: (predicted, reference_names, target_names, group_members) - the 6 members
+    of every subset as the dataset holds them, the reference among them (:298, :313)."""
+    q = relative_queries_from_dataset(relative_val_dataset, index_names, "cirr_val")
+    return _query_features(blip_model, q, index_features), q.reference_names, q.target_names, q.group_members
+
+
+def _check_topk(topk: Optional[int], n_index: int) -> int:
+    """The k to ask `rank_index_topk` for: its smallest (1) when only metrics are wanted."""
+    limit = min(2048, n_index - 1)
+    if topk is None:
+        return 1
+    if not 1 <= int(topk) <= limit:
+        raise ValueError(f"topk = {topk}: the top-K path holds 1 <= K <= min(2048, n_index - 1) = {limit}")
+    return int(topk)
+
+
+def _host(ranked):
+    return tuple(None if a is None else (a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)) for a in ranked)
+
+
+def group_index6(ref_index: np.ndarray, group_index: np.ndarray) -> np.ndarray:
+    """(Q, 6) groups incl. the reference, the layout `cirr_rank_cols` / `cirr_topk_from_ranks` read, from either that layout (the
+    dataset's) or the (Q, 5) members without the reference (RelativeValSet.group_index, RelativeQueries.group_index)."""
+    ref_index, group_index = np.asarray(ref_index), np.asarray(group_index)
+    if group_index.shape[1] == 6:
+        return group_index
+    if group_index.shape[1] != 5 or (group_index == ref_index[:, None]).any():
+        raise ValueError("group_index is (Q, 6) with the reference or (Q, 5) without it")
+    return np.concatenate([ref_index[:, None], group_index], axis=1)
+
+
+@torch.no_grad()
+def fiq_metrics_from_predictions(predicted, index_pooled, target_index, index_names: Sequence[str], split: str, dress_types,
+                                 topk: Optional[int] = None, ranked=None):
+    """validate.py:53-99 from the query features on: (R@10, R@50); with `topk=K` ((R@10, R@50), the top-K dict of :87-94).  One
+    `rank_index_topk` call with `cols` = the target (no row is sorted, `n_index` has no ceiling); recalls are formed from the target's
+    rank in the reference's float32 arithmetic.  `dress_types`: the dataset's list (joined with ',' as :85 does) or that string.
+    `ranked`: the (topk, ranks) pair of that call where the caller already holds it - `predicted` / `index_pooled` are not read then."""
+    index_names = list(index_names)
+    target_index = np.asarray(target_index, dtype=np.int64)
+    k = _check_topk(topk, len(index_names))
+    if ranked is None:
+        ranked = rank_index_topk(predicted, index_pooled.to(predicted.device).float(), k, cols=target_index[:, None])
+    top_rows, rank = _host(ranked)
+    dress = dress_types if isinstance(dress_types, str) else ",".join(dress_types)
+    metrics, top = fiq_topk_from_ranks(top_rows, rank, target_index, index_names, k, split, dress)
+    return metrics if topk is None else (metrics, top)
+
+
+@torch.no_grad()
+def cirr_metrics_from_predictions(predicted, index_pooled, ref_index, target_index, group_index, index_names: Sequence[str], split: str,
+                                  topk: Optional[int] = None, ranked=None):
+    """validate.py:196-268 from the query features on: (Rs@1, Rs@2, Rs@3, R@1, R@5, R@10, R@50), the reference's order (:268); with
+    `topk=K` (that tuple, the top-K dict of :256-263).  One `rank_index_topk` call with `exclude` = the reference image (:207-210) and
+    `cols` = `cirr_rank_cols(...)`.  `group_index`: (Q, 6) incl. the reference or (Q, 5) without it; `ranked` as above."""
+    index_names = list(index_names)
+    ref_index, target_index = np.asarray(ref_index, dtype=np.int64), np.asarray(target_index, dtype=np.int64)
+    group6 = group_index6(ref_index, group_index)
+    k = _check_topk(topk, len(index_names))
+    if ranked is None:
+        ranked = rank_index_topk(predicted, index_pooled.to(predicted.device).float(), k, exclude=ref_index,
+                                 cols=cirr_rank_cols(ref_index, target_index, group6))
+    top_rows, ranks = _host(ranked)
+    metrics, top = cirr_topk_from_ranks(top_rows, ranks, ref_index, target_index, group6, index_names, k, split)
+    return metrics if topk is None else (metrics, top)
+
+
+def _check_save(topk, save_path) -> None:
+    if save_path is not None and topk is None:
+        raise ValueError("save_path needs topk=K: the number of columns the file keeps")
+
+
+def _finish(result, topk, save_path):
+    """`result` as the caller returns it; its last entry, the top-K dict, written to `save_path` where given."""
+    _check_save(topk, save_path)
+    if save_path is not None:
+        save_topk(save_path, result[-1])
+    return result
+
+
+def compute_fiq_val_metrics(relative_val_dataset, blip_model, index_features, index_features_normed_pooled, index_names: Sequence[str],
+                            topk: Optional[int] = None, save_path: Optional[str] = None):
+    """validate.py:33-99 in the reference's call form (stage1_train.py:244): (R@10, R@50).  `topk=K` also returns the top-K dict and
+    `save_path=` writes it - what the reference does through the SAVE_TOPK / K_VALUE / STAGE1_PATH globals and a breakpoint() (:80-95);
+    `split` and `dress_types` are the dataset's attributes, as there (:85-92)."""
+    _check_save(topk, save_path)
+    q = relative_queries_from_dataset(relative_val_dataset, index_names, "fiq_val")
+    predicted = _query_features(blip_model, q, index_features)
+    out = fiq_metrics_from_predictions(predicted, index_features_normed_pooled, q.target_index, index_names, relative_val_dataset.split,
+                                       relative_val_dataset.dress_types, topk=topk)
+    return _finish(out, topk, save_path)
+
+
+def compute_cirr_val_metrics(relative_val_dataset, blip_model, index_features, index_features_normed_pooled, index_names: Sequence[str],
+                             topk: Optional[int] = None, save_path: Optional[str] = None):
+    """validate.py:176-268 in the reference's call form (stage1_train.py:459; `cirr_val_retrieval(train=True)`, :329-332, over the
+    ~17 k images of the train split likewise): the 7 metrics; `topk=K` / `save_path=` as `compute_fiq_val_metrics` (:249-264)."""
+    _check_save(topk, save_path)
+    q = relative_queries_from_dataset(relative_val_dataset, index_names, "cirr_val")
+    predicted = _query_features(blip_model, q, index_features)
+    out = cirr_metrics_from_predictions(predicted, index_features_normed_pooled, q.ref_index, q.target_index, q.group_index, index_names,
+                                        relative_val_dataset.split, topk=topk)
+    return _finish(out, topk, save_path)

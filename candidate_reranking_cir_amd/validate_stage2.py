@@ -192,6 +192,36 @@ def relative_val_set_from_dataset(relative_val_dataset, index_names: Sequence[st
     return ds, refs, targets, (members_no_ref if cirr else None)
 
 
+def relative_test_set_from_dataset(relative_test_dataset, index_names: Sequence[str]):
+    """The sibling of `relative_val_set_from_dataset` for the CIRR test1 split with its top-K file: items laid out as
+    data_utils.py:346 (pair_id, reference, caption, 6 group members incl. the reference, top-K names) ->
+    (RelativeValSet, reference names, group members without the reference, pair ids).  No labels exist on the test split: every
+    query is scored (cirr_test_submission_stage2.py:138-176 has no skip rule), so `labels` is all true and `target_index` None."""
+    row = {str(n): i for i, n in enumerate(index_names)}
+    if len(row) != len(index_names):
+        raise ValueError("index_names holds duplicates")
+    if not hasattr(relative_test_dataset, "K"):
+        raise TypeError("a stage-II CIRR test dataset has K and 5 fields per item (data_utils.py:305, 346): was it built with load_topk= / K= ?")
+    n_q, k = len(relative_test_dataset), int(relative_test_dataset.K)
+    refs, caps, members_no_ref, pair_ids = [], [], [], []
+    ref_index, cand_index = np.empty(n_q, dtype=np.int64), np.empty((n_q, k), dtype=np.int64)
+    for q in range(n_q):
+        item = relative_test_dataset[q]
+        if len(item) != 5:
+            raise TypeError(f"a stage-II CIRR test item has 5 fields (pair_id, reference, caption, 6 group members, top-K names), got {len(item)} "
+                            "(was the dataset built with load_topk= / K= ?)")
+        pair_id, ref, cap, members, k_names = item
+        pair_ids.append(pair_id); refs.append(str(ref)); caps.append(str(cap))
+        members_no_ref.append([str(m) for m in members if str(m) != str(ref)])             # cirr_test_submission_stage2.py:166, 173
+        ref_index[q] = row[str(ref)]
+        cand_index[q] = [row[str(n)] for n in k_names]
+    if any(len(m) != 5 for m in members_no_ref):
+        raise ValueError("every CIRR subset has 5 members besides the reference (cirr_test_submission_stage2.py:97)")
+    group_index = np.array([[row[m] for m in ms] for ms in members_no_ref], dtype=np.int64).reshape(n_q, 5)
+    ds = RelativeValSet(ref_index=ref_index, cand_index=cand_index, labels=np.ones((n_q, k), dtype=bool), captions=caps, group_index=group_index)
+    return ds, refs, members_no_ref, pair_ids
+
+
 def _bank16(blip_model, index_features: torch.Tensor) -> torch.Tensor:
     """The reference hands fp32 index features (utils.py:43-55); the scoring path reads the 16-bit bank: one conversion launch."""
     dt = getattr(blip_model, "token_dtype", blip_model.compute_dtype)
