@@ -81,23 +81,9 @@
 // 6 address adds per 8 MFMAs): 577 tokens now run at 597 TFLOP/s = 0.24 of the MFMA peak, 197 tokens at 0.13-0.16.
 
 #include <type_traits>
-#include "attention_args.hpp"
+#include "attn_tile.hpp"
 
 namespace cir {
-
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
-// Online-softmax state of one 32-query tile: lane = (query r, key/dh half hh).
-struct Softmax {
-    float m_run, l_run;
-    f32x16 o[2];
-    __device__ __forceinline__ void init() {
-        m_run = -INFINITY;
-        l_run = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { o[0][i] = 0.f; o[1][i] = 0.f; }
-    }
-};
 
 // raw scores -> probabilities, running max / sum (log2 domain), rescale of O; returns P^T packed.
 // MASKED = false (ViT, and text-side calls without a mask): the scale rides in the exponent's FMA,
@@ -111,7 +97,7 @@ __device__ __forceinline__ void softmax_tile(Softmax& st, f32x16& s, float sl, c
     if constexpr (MASKED) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int key = key0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+            const int key = key0 + acc_row(i, hh);
             // clamp keeps finfo.min-style masks finite in the log2 domain (all-masked rows stay uniform, like the reference)
             sv[i] = fmaf(fmaxf(mp[min(key, Lk - 1)], -2.0e38f), kLog2e, s[i] * sl);
         }
@@ -122,7 +108,7 @@ __device__ __forceinline__ void softmax_tile(Softmax& st, f32x16& s, float sl, c
     if (key0 + 32 > Lk) {   // wave-uniform: only the last key tile is ragged
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int key = key0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+            const int key = key0 + acc_row(i, hh);
             sv[i] = key < Lk ? sv[i] : -INFINITY;
         }
     }
@@ -178,56 +164,6 @@ __device__ __forceinline__ void softmax_tile(Softmax& st, f32x16& s, float sl, c
     for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
         for (int j = 0; j < 8; ++j) pf[s2][j] = static_cast<T>(sv[8 * s2 + j]);
-}
-
-// O^T += V_tile^T * P^T with V row-major in LDS at `vt` (128-byte rows, 64-byte halves swapped on rows with
-// bit 1 set so that the 4-row transposed reads of a 32-lane half hit 64 distinct banks).  `voff[dt]` = this lane's
-// byte offset inside a tile for dh-tile dt (tile-invariant: computed once per wave, see pv_lane_offsets); the two
-// key halves and the two 8-row blocks of a read pair are immediate offsets.
-template <typename T>
-__device__ __forceinline__ void pv_tile(Softmax& st, const char* vt, const int (&voff)[2], const typename Elem<T>::x8 (&pf)[2]) {
-    using X8 = typename Elem<T>::x8;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
-        const char* base0 = vt + voff[dt];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const char* base = base0 + (16 * s2) * 128;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + 8 * 128));
-            s16x8 both;
-            both.s0 = lo.x; both.s1 = lo.y; both.s2 = lo.z; both.s3 = lo.w;
-            both.s4 = hi.x; both.s5 = hi.y; both.s6 = hi.z; both.s7 = hi.w;
-            st.o[dt] = Elem<T>::mfma32(__builtin_bit_cast(X8, both), pf[s2], st.o[dt]);
-        }
-    }
-}
-__device__ __forceinline__ void pv_lane_offsets(int tr_lane_off, int (&voff)[2]) {
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) voff[dt] = ((tr_lane_off & 0x7f) ^ (dt * 64)) + (tr_lane_off & ~0x7f);
-}
-
-// this lane's address inside a 4-key x 16-dh transposed-read block (without the dh-tile term):
-// row (4*hh + q), byte column (16*(G&1) + 4p)*2, halves swapped when the row's bit 1 is set (row = 4*hh' + q, q>>1)
-__device__ __forceinline__ int tr_lane_offset(int lane) {
-    const int i16 = lane & 15, hh = lane >> 5;
-    const int q = i16 >> 2, p = i16 & 3;
-    const int col = ((16 * ((lane >> 4) & 1) + 4 * p) * 2) ^ ((q >> 1) << 6);
-    return (4 * hh + q) * 128 + col;
-}
-
-template <typename T>
-__device__ __forceinline__ void store_out(const Softmax& st, T* op /* row base + h*64 + 4*hh */) {
-    const float inv = 1.0f / st.l_run;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-            u32x2 p;
-            p.x = pack2<T>(st.o[dt][qd * 4 + 0] * inv, st.o[dt][qd * 4 + 1] * inv);
-            p.y = pack2<T>(st.o[dt][qd * 4 + 2] * inv, st.o[dt][qd * 4 + 3] * inv);
-            *reinterpret_cast<u32x2*>(op + dt * 32 + 8 * qd) = p;
-        }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -287,7 +223,7 @@ __global__ __launch_bounds__(1024) void attn_shared_kernel(const AttnArgs a, int
                 const int row = c >> 3, ch = c & 7;
                 if (c < nchunks) {
                     *reinterpret_cast<X8*>(Ks + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = kv[i];
-                    *reinterpret_cast<X8*>(Vs + row * 128 + ((ch * 16) ^ (((row >> 1) & 1) << 6))) = vv[i];
+                    *reinterpret_cast<X8*>(Vs + v_tile_offset(row, ch)) = vv[i];
                 }
             }
         }
@@ -297,7 +233,7 @@ __global__ __launch_bounds__(1024) void attn_shared_kernel(const AttnArgs a, int
     __syncthreads();
 
     int voff[2];
-    pv_lane_offsets(tr_lane_offset(lane), voff);
+    tr_offsets(lane, voff);
     // K fragment addresses: row (key0 + r), chunk (2*sx + hh) ^ ((row >> 1) & 7); key0 is a multiple of 32, so the swizzle
     // term depends on the lane only - four tile-invariant byte offsets per lane, one add per tile
     int koff[4];
@@ -328,12 +264,12 @@ __global__ __launch_bounds__(1024) void attn_shared_kernel(const AttnArgs a, int
             }
             X8 pf[2];
             softmax_tile<T, MASKED>(st, s, sl, mp, key0, hh, a.Lk, pf);
-            pv_tile<T>(st, vt_base, voff, pf);
+            tr_accumulate<T>(st.o, vt_base, voff, pf);
         }
         if (!a.wide_store) {             // several query tiles per wave (577 tokens), odd alignments: direct stores - 8-byte pieces, 32 rows per instruction
             if (q0 + r < a.Lq) {
                 T* op = reinterpret_cast<T*>(a.out) + b1 * a.o_s1 + b0 * a.o_s0 + (int64_t)(q0 + r) * a.o_rs + h * 64 + 4 * hh;
-                store_out<T>(st, op);
+                store_out<T>(st.o, op, 1.0f / st.l_run);
             }
         } else {
             // ONE tile per wave (197 tokens): the O tile goes out through LDS as WHOLE 128-byte rows (round 5).  The direct form writes a row's
@@ -348,11 +284,8 @@ __global__ __launch_bounds__(1024) void attn_shared_kernel(const AttnArgs a, int
             for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                 for (int qd = 0; qd < 4; ++qd) {
-                    u32x2 p;
-                    p.x = pack2<T>(st.o[dt][qd * 4 + 0] * inv, st.o[dt][qd * 4 + 1] * inv);
-                    p.y = pack2<T>(st.o[dt][qd * 4 + 2] * inv, st.o[dt][qd * 4 + 3] * inv);
                     const int col = dt * 32 + 8 * qd + 4 * hh;                      // first of this piece's 4 features
-                    *reinterpret_cast<u32x2*>(ot + r * 128 + ((((col >> 3) ^ (r & 7)) << 4) | ((col & 7) << 1))) = p;
+                    *reinterpret_cast<u32x2*>(ot + r * 128 + ((((col >> 3) ^ (r & 7)) << 4) | ((col & 7) << 1))) = pack4<T>(st.o[dt], qd, inv);
                 }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -376,47 +309,30 @@ __global__ __launch_bounds__(256) void attn_stream_kernel(const AttnArgs a) {
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t unit = (int64_t)blockIdx.x * 4 + wave;
-    if (unit >= a.total) return;  // whole wave leaves: EXEC stays all-ones for the transposed LDS reads
-
-    const int qt = (int)(unit % a.nqt);
-    int64_t t = unit / a.nqt;
-    const int h = (int)(t % a.H);
-    t /= a.H;
-    const int b0 = (int)(t % a.B0);
-    const int64_t b1 = t / a.B0;
+    AttnUnit u;
+    if (!u.decode(a, wave)) return;
 
     const int r = lane & 31, hh = lane >> 5;
-    const int q0 = qt * 32;
-    const int qrow = min(q0 + r, a.Lq - 1);
-    const T* qp = reinterpret_cast<const T*>(a.q) + b1 * a.q_s1 + b0 * a.q_s0 + (int64_t)qrow * a.q_rs + h * 64 + 8 * hh;
-    const int64_t kb1 = a.kv_index ? a.kv_index[b1] : b1;
-    const T* kb = reinterpret_cast<const T*>(a.k) + kb1 * a.k_s1 + b0 * a.k_s0 + h * 64 + 8 * hh;
-    const T* vb = reinterpret_cast<const T*>(a.v) + kb1 * a.v_s1 + b0 * a.v_s0 + h * 64;
-    const float* mp = MASKED ? a.mask + b1 * a.m_s1 + b0 * a.m_s0 : nullptr;
+    const int q0 = u.qt * 32;
+    const int64_t kb1 = u.kv_item(a);
+    const T* kb = u.k_base<T>(a, kb1) + 8 * hh;
+    const T* vb = u.v_base<T>(a, kb1);
+    const float* mp = MASKED ? u.mask_base(a) : nullptr;
 
     X8 qf[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const X8*>(qp + 16 * s);
+    frag_load<T>(u.q_row<T>(a, min(q0 + r, a.Lq - 1)) + 8 * hh, qf);
 
     char* vl = smem + wave * 4096;
     int voff[2];
-    pv_lane_offsets(tr_lane_offset(lane), voff);
+    tr_offsets(lane, voff);
     const float sl = a.scale * kLog2e;
     const int nkt = (a.Lk + 31) >> 5;
-    // V staging: lane covers 16-byte chunks c = lane + 64 i -> row c>>3, chunk c&7 (rows clamped: probability 0 there)
-    const int vrow_l = lane >> 3, vch = lane & 7;
 
+    // K fragments straight into registers, the V tile's chunks for the LDS copy (rows clamped: probability 0 there)
     auto load_tile = [&](int kt, X8 (&kf)[4], X8 (&vr)[4]) {
         const int key0 = kt * 32;
-        const T* kp = kb + (int64_t)min(key0 + r, a.Lk - 1) * a.k_rs;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) kf[s] = *reinterpret_cast<const X8*>(kp + 16 * s);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int vrow = min(key0 + vrow_l + 8 * i, a.Lk - 1);
-            vr[i] = *reinterpret_cast<const X8*>(vb + (int64_t)vrow * a.v_rs + vch * 8);
-        }
+        frag_load<T>(kb + (int64_t)min(key0 + r, a.Lk - 1) * a.k_rs, kf);
+        tile_load<T>(vb, a.v_rs, key0, a.Lk, lane, vr);
     };
 
     Softmax st;
@@ -430,24 +346,16 @@ __global__ __launch_bounds__(256) void attn_stream_kernel(const AttnArgs a) {
         for (int i = 0; i < 16; ++i) s[i] = 0.f;
 #pragma unroll
         for (int sx = 0; sx < 4; ++sx) s = Elem<T>::mfma32(kf[sx], qf[sx], s);
-        // V tile -> this wave's LDS tile (same row / half swizzle as the shared kernel)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = vrow_l + 8 * i;
-            *reinterpret_cast<X8*>(vl + row * 128 + ((vch * 16) ^ (((row >> 1) & 1) << 6))) = vr[i];
-        }
+        tile_store<T>(vl, lane, vr);                   // V tile -> this wave's LDS tile (same row / half swizzle as the shared kernel)
         if (kt + 1 < nkt) load_tile(kt + 1, kf, vr);   // prefetch the next tile under this tile's softmax / PV
         X8 pf[2];
         softmax_tile<T, MASKED>(st, s, sl, mp, key0, hh, a.Lk, pf);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        pv_tile<T>(st, vl, voff, pf);
+        tr_accumulate<T>(st.o, vl, voff, pf);
         __builtin_amdgcn_wave_barrier();  // keep the next tile's LDS writes behind these reads
     }
-    if (q0 + r < a.Lq) {
-        T* op = reinterpret_cast<T*>(a.out) + b1 * a.o_s1 + b0 * a.o_s0 + (int64_t)(q0 + r) * a.o_rs + h * 64 + 4 * hh;
-        store_out<T>(st, op);
-    }
+    if (q0 + r < a.Lq) store_out<T>(st.o, u.out_base<T>(a) + (int64_t)(q0 + r) * a.o_rs + u.h * 64 + 4 * hh, 1.0f / st.l_run);
 }
 
 
@@ -465,21 +373,14 @@ __global__ __launch_bounds__(256) void attn_split32_kernel(const AttnArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[4 * 2 * 4096];   // per wave: V_hi tile, V_lo tile (32 keys x 64 dh each)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t unit = (int64_t)blockIdx.x * 4 + wave;
-    if (unit >= a.total) return;
-    const int qt = (int)(unit % a.nqt);
-    int64_t t = unit / a.nqt;
-    const int h = (int)(t % a.H);
-    t /= a.H;
-    const int b0 = (int)(t % a.B0);
-    const int64_t b1 = t / a.B0;
+    AttnUnit u;
+    if (!u.decode(a, wave)) return;
     const int r = lane & 31, hh = lane >> 5;
-    const int q0 = qt * 32;
-    const int qrow = min(q0 + r, a.Lq - 1);
-    const float* qp = reinterpret_cast<const float*>(a.q) + b1 * a.q_s1 + b0 * a.q_s0 + (int64_t)qrow * a.q_rs + h * 64 + 8 * hh;
-    const float* kb = reinterpret_cast<const float*>(a.k) + b1 * a.k_s1 + b0 * a.k_s0 + h * 64 + 8 * hh;
-    const float* vb = reinterpret_cast<const float*>(a.v) + b1 * a.v_s1 + b0 * a.v_s0 + h * 64;
-    const float* mp = MASKED ? a.mask + b1 * a.m_s1 + b0 * a.m_s0 : nullptr;
+    const int q0 = u.qt * 32;
+    const float* qp = u.q_row<float>(a, min(q0 + r, a.Lq - 1)) + 8 * hh;
+    const float* kb = u.k_base<float>(a, u.b1) + 8 * hh;      // (no K / V bank in this entry point)
+    const float* vb = u.v_base<float>(a, u.b1);
+    const float* mp = MASKED ? u.mask_base(a) : nullptr;
 
     // eight consecutive fp32 values -> (hi, lo) fp16 fragments
     auto split = [](const float4& x0, const float4& x1, X8& hi, X8& lo) {
@@ -499,7 +400,7 @@ __global__ __launch_bounds__(256) void attn_split32_kernel(const AttnArgs a) {
     char* vt_hi = smem + wave * 8192;
     char* vt_lo = vt_hi + 4096;
     int voff[2];
-    pv_lane_offsets(tr_lane_offset(lane), voff);
+    tr_offsets(lane, voff);
     const float sl = a.scale * kLog2e;
     const int nkt = (a.Lk + 31) >> 5;
     const int vrow_l = lane >> 3, vch = lane & 7;
@@ -536,38 +437,13 @@ __global__ __launch_bounds__(256) void attn_split32_kernel(const AttnArgs a) {
         for (int i = 0; i < 4; ++i) {
             X8 vh, vl;
             split(vr[i][0], vr[i][1], vh, vl);
-            const int row = vrow_l + 8 * i;
-            const int off = row * 128 + ((vch * 16) ^ (((row >> 1) & 1) << 6));
+            const int off = v_tile_offset(vrow_l + 8 * i, vch);
             *reinterpret_cast<X8*>(vt_hi + off) = vh;
             *reinterpret_cast<X8*>(vt_lo + off) = vl;
         }
         if (kt + 1 < nkt) load_tile(kt + 1);
-        // ---- online softmax (log2 domain), probabilities kept in fp32 ----
-        float sv[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int key = key0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-            float x = s[i] * sl;
-            if constexpr (MASKED) x = fmaf(fmaxf(mp[min(key, a.Lk - 1)], -2.0e38f), kLog2e, x);
-            sv[i] = key < a.Lk ? x : -INFINITY;
-        }
-        float mx = sv[0];
-#pragma unroll
-        for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sv[i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(st.m_run, mx);
-        const float alpha = exp2f(st.m_run - m_new);
-        st.m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            sv[i] = exp2f(sv[i] - m_new);
-            psum += sv[i];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        st.l_run = st.l_run * alpha + psum;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { st.o[0][i] *= alpha; st.o[1][i] *= alpha; }
+        float sv[16];                                  // probabilities kept in fp32
+        softmax_plain<MASKED>(st, s, sl, mp, key0, hh, a.Lk, sv);
         X8 ph[2], pl[2];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2)
@@ -579,32 +455,13 @@ __global__ __launch_bounds__(256) void attn_split32_kernel(const AttnArgs a) {
             }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        pv_tile<_Float16>(st, vt_lo, voff, ph);
-        pv_tile<_Float16>(st, vt_hi, voff, pl);
-        pv_tile<_Float16>(st, vt_hi, voff, ph);
+        tr_accumulate<_Float16>(st.o, vt_lo, voff, ph);
+        tr_accumulate<_Float16>(st.o, vt_hi, voff, pl);
+        tr_accumulate<_Float16>(st.o, vt_hi, voff, ph);
         __builtin_amdgcn_wave_barrier();
     }
-    // ---- context / row sum -> split8 rows (as attn_f32_kernel's SPLIT epilogue: the half-waves exchange 4-element groups) ----
-    const float inv = 1.0f / st.l_run;
-    const int d_model = a.H * 64;
-    char* row = reinterpret_cast<char*>(a.out) + b1 * a.o_s1 + b0 * a.o_s0 + (int64_t)min(q0 + r, a.Lq - 1) * a.o_rs;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            float lo4[4], hi4[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { lo4[j] = st.o[dt][(2 * p) * 4 + j] * inv; hi4[j] = st.o[dt][(2 * p + 1) * 4 + j] * inv; }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(lo4[j]), "+v"(hi4[j]));
-            const int f0 = h * 64 + dt * 32 + 8 * (2 * p + hh);
-            const Split4 s0 = split8_x4(lo4), s1 = split8_x4(hi4);
-            if (q0 + r < a.Lq) {
-                *reinterpret_cast<u32x4*>(row + 2 * f0) = u32x4{s0.h01, s0.h23, s1.h01, s1.h23};
-                *reinterpret_cast<u32x2*>(row + 2 * d_model + f0) = u32x2{s0.lo8, s1.lo8};
-                *reinterpret_cast<u32x2*>(row + 3 * d_model + f0) = u32x2{s0.hi8, s1.hi8};
-            }
-        }
+    // ---- context / row sum -> split8 rows (as attn_f32_kernel's SPLIT epilogue) ----
+    store_split8_rows(st.o, 1.0f / st.l_run, u.out_base<char>(a) + (int64_t)min(q0 + r, a.Lq - 1) * a.o_rs, a.H * 64, u.h * 64, hh, q0 + r < a.Lq);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -668,9 +525,7 @@ __global__ __launch_bounds__(256, 2) void cls_xattn_kernel(const T* __restrict__
 #pragma unroll
         for (int i = 0; i < 16; ++i) o[dt][i] = 0.f;
     const float sl = scale * kLog2e;
-    // transposed-read lane offset inside a 4-key x 16-column block (see tr_lane_offset), for this tile's row stride
-    const int i16 = lane & 15;
-    const int troff = (4 * hh + (i16 >> 2)) * RS + (16 * ((lane >> 4) & 1) + 4 * (i16 & 3)) * 2 + wave * SL * 2;
+    const int troff = tr_block_offset(lane, RS) + wave * SL * 2;    // this tile's rows are padded, not swizzled
 
     load_tile(0);
     for (int kt = 0; kt < nkt; ++kt) {
@@ -697,7 +552,7 @@ __global__ __launch_bounds__(256, 2) void cls_xattn_kernel(const T* __restrict__
         const int key0 = kt * 32;
         if (key0 + 32 > Lk) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) sv[i] = (key0 + (i & 3) + 8 * (i >> 2) + 4 * hh) < Lk ? sv[i] : -INFINITY;
+            for (int i = 0; i < 16; ++i) sv[i] = key0 + acc_row(i, hh) < Lk ? sv[i] : -INFINITY;
         }
         float mx = sv[0];
 #pragma unroll
@@ -725,28 +580,38 @@ __global__ __launch_bounds__(256, 2) void cls_xattn_kernel(const T* __restrict__
 #pragma unroll
             for (int i = 0; i < 16; ++i) o[dt][i] *= alpha;
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const char* base = xs + troff + dt * 64 + (16 * s2) * RS;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(base + 8 * RS));
-                s16x8 both;
-                both.s0 = lo.x; both.s1 = lo.y; both.s2 = lo.z; both.s3 = lo.w;
-                both.s4 = hi.x; both.s5 = hi.y; both.s6 = hi.z; both.s7 = hi.w;
-                o[dt] = Elem<T>::mfma32(__builtin_bit_cast(X8, both), pf[s2], o[dt]);
-            }
+            for (int s2 = 0; s2 < 2; ++s2) o[dt] = Elem<T>::mfma32(tr_read8<T>(xs + troff + dt * 64 + (16 * s2) * RS, RS), pf[s2], o[dt]);
         }
     }
-    const float inv = 1.0f / l_run;
-    T* op = ob + r * D + wave * SL + 4 * hh;
-#pragma unroll
-    for (int dt = 0; dt < NO; ++dt)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) {
-            u32x2 p;
-            p.x = pack2<T>(o[dt][qd * 4 + 0] * inv, o[dt][qd * 4 + 1] * inv);
-            p.y = pack2<T>(o[dt][qd * 4 + 2] * inv, o[dt][qd * 4 + 3] * inv);
-            *reinterpret_cast<u32x2*>(op + dt * 32 + 8 * qd) = p;
-        }
+    store_out<T>(o, ob + r * D + wave * SL + 4 * hh, 1.0f / l_run);
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------
+struct HeadView { const void* p; int64_t s1, s0, rs; };     // (B1, B0, rows, H*64) view: base and item / inner item / row strides
+
+static AttnArgs fill_attn_args(const HeadView& q, const HeadView& k, const HeadView& v, const float* mask, int64_t m_s1, int64_t m_s0,
+                               const int64_t* kv_index, void* out, int64_t o_s1, int64_t o_s0, int64_t o_rs, int B1, int B0, int H, int Lq, int Lk,
+                               float scale) {
+    AttnArgs a;
+    a.q = q.p; a.q_s1 = q.s1; a.q_s0 = q.s0; a.q_rs = q.rs;
+    a.k = k.p; a.k_s1 = k.s1; a.k_s0 = k.s0; a.k_rs = k.rs;
+    a.v = v.p; a.v_s1 = v.s1; a.v_s0 = v.s0; a.v_rs = v.rs;
+    a.mask = mask; a.m_s1 = m_s1; a.m_s0 = m_s0;
+    a.kv_index = kv_index;
+    a.out = out; a.o_s1 = o_s1; a.o_s0 = o_s0; a.o_rs = o_rs;
+    a.B0 = B0; a.H = H; a.Lq = Lq; a.Lk = Lk; a.nqt = (Lq + 31) / 32;
+    a.total = (int64_t)B1 * B0 * H * a.nqt;
+    a.scale = scale;
+    a.wide_store = 0;
+    return a;
+}
+
+// f(type tag, mask constant) for the 16-bit operand type and the presence of a mask
+template <typename T> struct TypeTag { using type = T; };
+template <typename F>
+static int by_dtype_mask(int dtype, bool masked, F&& f) {
+    if (dtype == CIR_BF16) return masked ? f(TypeTag<__bf16>{}, std::true_type{}) : f(TypeTag<__bf16>{}, std::false_type{});
+    return masked ? f(TypeTag<_Float16>{}, std::true_type{}) : f(TypeTag<_Float16>{}, std::false_type{});
 }
 
 }  // namespace cir
@@ -765,17 +630,8 @@ extern "C" int cir_attention(const void* q, int64_t q_s1, int64_t q_s0, int64_t 
         if (s % vec) return CIR_EALIGN;
     if (o_s1 % 4 || o_s0 % 4 || o_rs % 4) return CIR_EALIGN;
     if (!cir_aligned16(q) || !cir_aligned16(k) || !cir_aligned16(v) || (reinterpret_cast<uintptr_t>(out) & (dtype == CIR_F32 ? 15 : 7))) return CIR_EALIGN;
-    AttnArgs a;
-    a.q = q; a.q_s1 = q_s1; a.q_s0 = q_s0; a.q_rs = q_rs;
-    a.k = k; a.k_s1 = k_s1; a.k_s0 = k_s0; a.k_rs = k_rs;
-    a.v = v; a.v_s1 = v_s1; a.v_s0 = v_s0; a.v_rs = v_rs;
-    a.mask = mask; a.m_s1 = m_s1; a.m_s0 = m_s0;
-    a.kv_index = kv_index;
-    a.out = out; a.o_s1 = o_s1; a.o_s0 = o_s0; a.o_rs = o_rs;
-    a.B0 = B0; a.H = H; a.Lq = Lq; a.Lk = Lk; a.nqt = (Lq + 31) / 32;
-    a.total = (int64_t)B1 * B0 * H * a.nqt;
-    a.scale = scale;
-    a.wide_store = 0;
+    AttnArgs a = fill_attn_args({q, q_s1, q_s0, q_rs}, {k, k_s1, k_s0, k_rs}, {v, v_s1, v_s0, v_rs}, mask, m_s1, m_s0, kv_index, out, o_s1, o_s0, o_rs,
+                                B1, B0, H, Lq, Lk, scale);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == CIR_F32) return launch_attention_f32(a, s);      // "exact" mode: fp32 operands in both products (attention_f32.hip)
     const int lk_pad = (Lk + 31) & ~31;
@@ -806,24 +662,23 @@ extern "C" int cir_attention(const void* q, int64_t q_s1, int64_t q_s0, int64_t 
         // whole-row output stores through the (then dead) K / V region: exactly one tile per wave (every wave reaches the barrier once),
         // 16-byte-aligned output rows, 4 KiB of LDS per wave
         a.wide_store = rounds == 1 && waves == a.nqt && (size_t)waves * 4096 <= lds && cir_aligned16(out) && o_s1 % 8 == 0 && o_s0 % 8 == 0 && o_rs % 8 == 0;
-        const bool bf = dtype == CIR_BF16, mk = mask != nullptr;
-        const void* fn = bf ? (mk ? reinterpret_cast<const void*>(&attn_shared_kernel<__bf16, true>) : reinterpret_cast<const void*>(&attn_shared_kernel<__bf16, false>))
-                            : (mk ? reinterpret_cast<const void*>(&attn_shared_kernel<_Float16, true>) : reinterpret_cast<const void*>(&attn_shared_kernel<_Float16, false>));
-        if (lds > 64 * 1024) {   // opt in to more than 64 KiB of dynamic LDS (idempotent, per function)
-            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-        }
-        if (bf) { if (mk) hipLaunchKernelGGL((attn_shared_kernel<__bf16, true>), grid, block, lds, s, a, lk_pad); else hipLaunchKernelGGL((attn_shared_kernel<__bf16, false>), grid, block, lds, s, a, lk_pad); }
-        else { if (mk) hipLaunchKernelGGL((attn_shared_kernel<_Float16, true>), grid, block, lds, s, a, lk_pad); else hipLaunchKernelGGL((attn_shared_kernel<_Float16, false>), grid, block, lds, s, a, lk_pad); }
-        CIR_LAUNCH_RESULT();
+        return by_dtype_mask(dtype, mask != nullptr, [&](auto t, auto mk) -> int {
+            auto* const kernel = &attn_shared_kernel<typename decltype(t)::type, decltype(mk)::value>;
+            if (lds > 64 * 1024) {   // opt in to more than 64 KiB of dynamic LDS (idempotent, per function)
+                const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) return (int)e;
+            }
+            hipLaunchKernelGGL(kernel, grid, block, lds, s, a, lk_pad);
+            CIR_LAUNCH_RESULT();
+        });
     }
     const int64_t nblk = (a.total + 3) / 4;
     if (nblk > 0x7fffffff) return CIR_ESHAPE;
     dim3 grid((unsigned)nblk), block(256);
-    const bool mk = mask != nullptr;
-    if (dtype == CIR_BF16) { if (mk) hipLaunchKernelGGL((attn_stream_kernel<__bf16, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((attn_stream_kernel<__bf16, false>), grid, block, 0, s, a); }
-    else { if (mk) hipLaunchKernelGGL((attn_stream_kernel<_Float16, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((attn_stream_kernel<_Float16, false>), grid, block, 0, s, a); }
-    CIR_LAUNCH_RESULT();
+    return by_dtype_mask(dtype, mask != nullptr, [&](auto t, auto mk) -> int {
+        hipLaunchKernelGGL((attn_stream_kernel<typename decltype(t)::type, decltype(mk)::value>), grid, block, 0, s, a);
+        CIR_LAUNCH_RESULT();
+    });
 }
 
 extern "C" int cir_attention_split8(const float* q, int64_t q_s1, int64_t q_s0, int64_t q_rs, const float* k, int64_t k_s1, int64_t k_s0, int64_t k_rs,
@@ -838,17 +693,8 @@ extern "C" int cir_attention_split8(const float* q, int64_t q_s1, int64_t q_s0, 
         if (s % 4) return CIR_EALIGN;
     if (o_s1_bytes % 16 || o_s0_bytes % 16 || o_rs_bytes % 16 || o_rs_bytes < 4 * (int64_t)H * 64) return CIR_EALIGN;
     if (!cir_aligned16(q) || !cir_aligned16(k) || !cir_aligned16(v) || !cir_aligned16(out)) return CIR_EALIGN;
-    AttnArgs a;
-    a.q = q; a.q_s1 = q_s1; a.q_s0 = q_s0; a.q_rs = q_rs;
-    a.k = k; a.k_s1 = k_s1; a.k_s0 = k_s0; a.k_rs = k_rs;
-    a.v = v; a.v_s1 = v_s1; a.v_s0 = v_s0; a.v_rs = v_rs;
-    a.mask = mask; a.m_s1 = m_s1; a.m_s0 = m_s0;
-    a.kv_index = nullptr;
-    a.out = out; a.o_s1 = o_s1_bytes; a.o_s0 = o_s0_bytes; a.o_rs = o_rs_bytes;
-    a.B0 = B0; a.H = H; a.Lq = Lq; a.Lk = Lk; a.nqt = (Lq + 31) / 32;
-    a.total = (int64_t)B1 * B0 * H * a.nqt;
-    a.scale = scale;
-    a.wide_store = 0;
+    AttnArgs a = fill_attn_args({q, q_s1, q_s0, q_rs}, {k, k_s1, k_s0, k_rs}, {v, v_s1, v_s0, v_rs}, mask, m_s1, m_s0, nullptr, out, o_s1_bytes, o_s0_bytes,
+                                o_rs_bytes, B1, B0, H, Lq, Lk, scale);
     a.out_split = 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (g_tune[CIR_TUNE_ATTN_SHARED_MAX] == -2) return launch_attention_f32(a, s);   // (A/B and tests: the f32-input MFMA form of the same op)

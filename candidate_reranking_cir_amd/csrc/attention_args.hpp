@@ -18,8 +18,6 @@ struct AttnArgs {
     int out_split = 0;         // attn_f32_kernel: `out` receives "split8" rows (common.hpp; o_s1 / o_s0 / o_rs in BYTES) instead of fp32
 };
 
-constexpr float kLog2e = 1.4426950408889634f;
-
 // one wave per (item, head, 32 queries) on v_mfma_f32_32x32x2_f32; returns a CIR_* / hipError_t code
 int launch_attention_f32(const AttnArgs& a, hipStream_t s);
 

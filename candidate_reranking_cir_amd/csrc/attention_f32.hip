@@ -14,7 +14,7 @@
 // Replaces BertSelfAttention.forward (nlvr_encoder.py:140-222, med.py:158-240) and Attention.forward's core (vit.py:73-83) when every
 // tensor of the model is fp32, like the reference's (validate_stage2.py:140-141).
 
-#include "attention_args.hpp"
+#include "attn_tile.hpp"
 
 namespace cir {
 
@@ -25,24 +25,16 @@ template <bool MASKED, bool SPLIT = false>
 __global__ __launch_bounds__(256, 2) void attn_f32_kernel(const AttnArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t unit = (int64_t)blockIdx.x * 4 + wave;
-    if (unit >= a.total) return;
-
-    const int qt = (int)(unit % a.nqt);
-    int64_t t = unit / a.nqt;
-    const int h = (int)(t % a.H);
-    t /= a.H;
-    const int b0 = (int)(t % a.B0);
-    const int64_t b1 = t / a.B0;
+    AttnUnit u;
+    if (!u.decode(a, wave)) return;
 
     const int r = lane & 31, hh = lane >> 5;
-    const int q0 = qt * 32;
-    const int qrow = min(q0 + r, a.Lq - 1);
-    const float* qp = reinterpret_cast<const float*>(a.q) + b1 * a.q_s1 + b0 * a.q_s0 + (int64_t)qrow * a.q_rs + h * 64 + 4 * hh;
-    const int64_t kb1 = a.kv_index ? a.kv_index[b1] : b1;
-    const float* kb = reinterpret_cast<const float*>(a.k) + kb1 * a.k_s1 + b0 * a.k_s0 + h * 64 + 4 * hh;
-    const float* vb = reinterpret_cast<const float*>(a.v) + kb1 * a.v_s1 + b0 * a.v_s0 + h * 64 + r;
-    const float* mp = MASKED ? a.mask + b1 * a.m_s1 + b0 * a.m_s0 : nullptr;
+    const int q0 = u.qt * 32;
+    const float* qp = u.q_row<float>(a, min(q0 + r, a.Lq - 1)) + 4 * hh;
+    const int64_t kb1 = u.kv_item(a);
+    const float* kb = u.k_base<float>(a, kb1) + 4 * hh;
+    const float* vb = u.v_base<float>(a, kb1) + r;
+    const float* mp = MASKED ? u.mask_base(a) : nullptr;
 
     f32x4 qf[8];
 #pragma unroll
@@ -57,17 +49,15 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(const AttnArgs a) {
     auto load_v = [&](int kt, float (&vf)[2][16]) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int key = min(kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh, a.Lk - 1);     // rows past Lk: probability 0, any finite value
+            const int key = min(kt * 32 + acc_row(i, hh), a.Lk - 1);     // rows past Lk: probability 0, any finite value
             const float* vp = vb + (int64_t)key * a.v_rs;
             vf[0][i] = vp[0];
             vf[1][i] = vp[32];
         }
     };
 
-    float m_run = -INFINITY, l_run = 0.f;
-    f32x16 o[2];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { o[0][i] = 0.f; o[1][i] = 0.f; }
+    Softmax st;
+    st.init();
     const float sl = a.scale * kLog2e;
 
     f32x4 kf[8];
@@ -84,74 +74,20 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(const AttnArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[c][e], qf[c][e], s, 0, 0, 0);
         if (kt + 1 < nkt) load_k(kt + 1, kf);
-        // ---- online softmax in the log2 domain: lane = query r, 16 of the tile's 32 keys ----
         float sv[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int key = key0 + (i & 3) + 8 * (i >> 2) + 4 * hh;
-            float x = s[i] * sl;
-            if constexpr (MASKED) x = fmaf(fmaxf(mp[min(key, a.Lk - 1)], -2.0e38f), kLog2e, x);    // finfo.min-style masks stay finite
-            sv[i] = key < a.Lk ? x : -INFINITY;
-        }
-        float mx = sv[0];
-#pragma unroll
-        for (int i = 1; i < 16; ++i) mx = fmaxf(mx, sv[i]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);             // finite: every tile holds at least one valid key
-        const float alpha = exp2f(m_run - m_new);
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            sv[i] = exp2f(sv[i] - m_new);
-            psum += sv[i];
-        }
-        psum += __shfl_xor(psum, 32, 64);
-        l_run = l_run * alpha + psum;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { o[0][i] *= alpha; o[1][i] *= alpha; }
+        softmax_plain<MASKED>(st, s, sl, mp, key0, hh, a.Lk, sv);
         // ---- O^T += V_tile^T P^T ----
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[0][i], sv[i], o[0], 0, 0, 0);
-            o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[1][i], sv[i], o[1], 0, 0, 0);
+            st.o[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[0][i], sv[i], st.o[0], 0, 0, 0);
+            st.o[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[1][i], sv[i], st.o[1], 0, 0, 0);
         }
         if (kt + 1 < nkt) load_v(kt + 1, vf);
     }
-    if constexpr (SPLIT) {
-        const float inv = 1.0f / l_run;
-        const int d_model = a.H * 64;
-        char* row = reinterpret_cast<char*>(a.out) + b1 * a.o_s1 + b0 * a.o_s0 + (int64_t)min(q0 + r, a.Lq - 1) * a.o_rs;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                float lo4[4], hi4[4];          // own groups qd = 2p (features 8 qd + 4 hh + j) and qd = 2p + 1
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { lo4[j] = o[dt][(2 * p) * 4 + j] * inv; hi4[j] = o[dt][(2 * p + 1) * 4 + j] * inv; }
-                // swap: lanes 0-31 end with (own group 2p | partner's group 2p) = 8 consecutive features at 8 (2p); lanes 32-63 with
-                // (partner's group 2p+1 | own group 2p+1) = 8 consecutive features at 8 (2p+1)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(lo4[j]), "+v"(hi4[j]));
-                const int f0 = h * 64 + dt * 32 + 8 * (2 * p + hh);
-                const Split4 s0 = split8_x4(lo4), s1 = split8_x4(hi4);
-                if (q0 + r < a.Lq) {
-                    *reinterpret_cast<u32x4*>(row + 2 * f0) = u32x4{s0.h01, s0.h23, s1.h01, s1.h23};
-                    *reinterpret_cast<u32x2*>(row + 2 * d_model + f0) = u32x2{s0.lo8, s1.lo8};
-                    *reinterpret_cast<u32x2*>(row + 3 * d_model + f0) = u32x2{s0.hi8, s1.hi8};
-                }
-            }
-    } else
-    if (q0 + r < a.Lq) {
-        const float inv = 1.0f / l_run;
-        float* op = reinterpret_cast<float*>(a.out) + b1 * a.o_s1 + b0 * a.o_s0 + (int64_t)(q0 + r) * a.o_rs + h * 64 + 4 * hh;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd)
-                *reinterpret_cast<float4*>(op + dt * 32 + 8 * qd) =
-                    make_float4(o[dt][qd * 4 + 0] * inv, o[dt][qd * 4 + 1] * inv, o[dt][qd * 4 + 2] * inv, o[dt][qd * 4 + 3] * inv);
-    }
+    if constexpr (SPLIT)
+        store_split8_rows(st.o, 1.0f / st.l_run, u.out_base<char>(a) + (int64_t)min(q0 + r, a.Lq - 1) * a.o_rs, a.H * 64, u.h * 64, hh, q0 + r < a.Lq);
+    else if (q0 + r < a.Lq)
+        store_f32(st.o, u.out_base<float>(a) + (int64_t)(q0 + r) * a.o_rs + u.h * 64 + 4 * hh, 1.0f / st.l_run);
 }
 
 int launch_attention_f32(const AttnArgs& a, hipStream_t s) {
@@ -163,8 +99,7 @@ int launch_attention_f32(const AttnArgs& a, hipStream_t s) {
         else hipLaunchKernelGGL((attn_f32_kernel<false, true>), grid, block, 0, s, a);
     } else if (a.mask) hipLaunchKernelGGL((attn_f32_kernel<true>), grid, block, 0, s, a);
     else hipLaunchKernelGGL((attn_f32_kernel<false>), grid, block, 0, s, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? CIR_OK : (int)e;
+    CIR_LAUNCH_RESULT();
 }
 
 }  // namespace cir

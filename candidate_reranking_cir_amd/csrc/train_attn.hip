@@ -3,8 +3,8 @@
 // dropout mask is regenerated from its counter) - no score / probability tensor ever exists in memory (the un-fused pass of round 3
 // materialised 9 GB of fp32 scores and their adjoints per step at 577 keys).  Head dimension 64, 16-bit operands, fp32 statistics.
 //
-// All three kernels are the streaming inference kernel's tile update (attention.hip: one wave per 32-row tile, the contraction partner
-// streamed in 32-row tiles, scores TRANSPOSED so that a lane owns one column and the packed probabilities are already the B operand of
+// All three kernels are the streaming inference kernel's tile update (attention.hip; the pieces are attn_tile.hpp's: one wave per 32-row tile, the
+// contraction partner streamed in 32-row tiles, scores TRANSPOSED so that a lane owns one column and the packed probabilities are already the B operand of
 // the next product, the other operand of that product read transposed from a row-major LDS tile with ds_read_b64_tr_b16) with the roles
 // of the tensors permuted:
 //   forward  wave = 32 queries, streams keys:  S^T = K Q^T      P^T = softmax            O^T  += V^T  Pd^T      (V tile in LDS)
@@ -15,12 +15,9 @@
 // their probabilities forced to zero.  Dropout: element (row = (group * H + head) * Lq + query, col = key) of common.hpp's pair hash.
 #include <type_traits>
 
-#include "common.hpp"
+#include "attn_tile.hpp"
 
 namespace cir {
-
-constexpr float kLog2eT = 1.4426950408889634f;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr_t;
 
 struct TAttnArgs {
     const void* q; int64_t q_sg, q_sh, q_sr;
@@ -39,75 +36,6 @@ struct TAttnArgs {
     float scale, p_drop;
     uint64_t seed;
 };
-
-// this lane's address inside a 4-row x 16-column transposed-read block (see attention.hip: tr_lane_offset / pv_lane_offsets)
-__device__ __forceinline__ void tr_offsets(int lane, int (&voff)[2]) {
-    const int i16 = lane & 15, hh = lane >> 5;
-    const int q = i16 >> 2, p = i16 & 3;
-    const int col = ((16 * ((lane >> 4) & 1) + 4 * p) * 2) ^ ((q >> 1) << 6);
-    const int off = (4 * hh + q) * 128 + col;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) voff[dt] = ((off & 0x7f) ^ (dt * 64)) + (off & ~0x7f);
-}
-
-// acc^T[64 dh][32 cols] += tile^T[dh][32 rows] * frag[rows][cols]: `tile` = 32 rows x 64 dh row-major in LDS (128-byte rows, halves swapped
-// on rows with bit 1 set), frag = the packed accumulator-layout values of the 32 x 32 score-like tile (k-slot order of attention.hip)
-template <typename T>
-__device__ __forceinline__ void tr_accumulate(f32x16 (&acc)[2], const char* tile, const int (&voff)[2], const typename Elem<T>::x8 (&frag)[2]) {
-    using X8 = typename Elem<T>::x8;
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt) {
-        const char* base0 = tile + voff[dt];
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const char* base = base0 + (16 * s2) * 128;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr_t)(base));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr_t)(base + 8 * 128));
-            s16x8 both;
-            both.s0 = lo.x; both.s1 = lo.y; both.s2 = lo.z; both.s3 = lo.w;
-            both.s4 = hi.x; both.s5 = hi.y; both.s6 = hi.z; both.s7 = hi.w;
-            acc[dt] = Elem<T>::mfma32(__builtin_bit_cast(X8, both), frag[s2], acc[dt]);
-        }
-    }
-}
-
-// row-major 32 x 64 tile of 16-bit rows (row r of the source at src + min(row0 + r, rows - 1) * stride) -> registers -> the wave's LDS tile
-template <typename T>
-__device__ __forceinline__ void tile_load(const T* src, int64_t stride, int row0, int rows, int lane, typename Elem<T>::x8 (&reg)[4]) {
-    using X8 = typename Elem<T>::x8;
-    const int rl = lane >> 3, ch = lane & 7;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) reg[i] = *reinterpret_cast<const X8*>(src + (int64_t)min(row0 + rl + 8 * i, rows - 1) * stride + ch * 8);
-}
-template <typename T>
-__device__ __forceinline__ void tile_store(char* tile, int lane, const typename Elem<T>::x8 (&reg)[4]) {
-    using X8 = typename Elem<T>::x8;
-    const int rl = lane >> 3, ch = lane & 7;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = rl + 8 * i;
-        *reinterpret_cast<X8*>(tile + row * 128 + ((ch * 16) ^ (((row >> 1) & 1) << 6))) = reg[i];
-    }
-}
-// fragments of rows (lane & 31) of a row-major matrix: d-chunks 8 hh + 16 s (A operand rows / B operand columns of mfma_f32_32x32x16)
-template <typename T>
-__device__ __forceinline__ void frag_load(const T* row_ptr, typename Elem<T>::x8 (&f)[4]) {
-    using X8 = typename Elem<T>::x8;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) f[s] = *reinterpret_cast<const X8*>(row_ptr + 16 * s);
-}
-// accumulator index i of a 32 x 32 tile -> row inside the tile (this lane's column is lane & 31)
-__device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
-
-// fp32 store of a transposed accumulator: element (row = lane & 31, dh = 32 dt + 8 qd + 4 hh + j)
-__device__ __forceinline__ void store_f32(const f32x16 (&acc)[2], float* rowp /* + 4 hh */, float mul) {
-#pragma unroll
-    for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd)
-            *reinterpret_cast<float4*>(rowp + dt * 32 + 8 * qd) =
-                make_float4(acc[dt][qd * 4 + 0] * mul, acc[dt][qd * 4 + 1] * mul, acc[dt][qd * 4 + 2] * mul, acc[dt][qd * 4 + 3] * mul);
-}
 
 // gradient store of a transposed accumulator (same element map) at element offset `off` of `base`: fp32 or the operand type
 template <typename T>
@@ -132,10 +60,9 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const TAttnArgs a) {
     __shared__ __attribute__((aligned(16))) char smem[4 * 4096];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t unit = (int64_t)blockIdx.x * 4 + wave;
-    if (unit >= (int64_t)a.G * a.H * a.nqt) return;
-    const int qt = (int)(unit % a.nqt);
-    const int64_t gh = unit / a.nqt;
+    int qt;
+    int64_t gh;
+    if (!wave_unit(wave, (int64_t)a.G * a.H * a.nqt, a.nqt, qt, gh)) return;
     const int h = (int)(gh % a.H);
     const int64_t g = gh / a.H;
     const int r = lane & 31, hh = lane >> 5;
@@ -149,7 +76,7 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const TAttnArgs a) {
     char* vl = smem + wave * 4096;
     int voff[2];
     tr_offsets(lane, voff);
-    const float sl = a.scale * kLog2eT;
+    const float sl = a.scale * kLog2e;
     const float keep = a.p_drop > 0.f ? 1.0f / (1.0f - a.p_drop) : 1.0f;
     const uint32_t rkey = drop_row_key(a.seed, (uint64_t)(gh * a.Lq + qrow)), thr = drop_threshold(a.p_drop);
 
@@ -178,7 +105,7 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const TAttnArgs a) {
         for (int i = 0; i < 16; ++i) {
             const int key = key0 + acc_row(i, hh);
             float x = s[i] * sl;
-            if constexpr (MASKED) x = fmaf(fmaxf(mp[min(key, a.Lk - 1)], -2.0e38f), kLog2eT, x);
+            if constexpr (MASKED) x = fmaf(fmaxf(mp[min(key, a.Lk - 1)], -2.0e38f), kLog2e, x);
             sv[i] = key < a.Lk ? x : -INFINITY;
             mx = fmaxf(mx, sv[i]);
         }
@@ -209,16 +136,7 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const TAttnArgs a) {
     }
     if (q0 + r < a.Lq) {
         const float inv = 1.0f / l_run;
-        T* op = const_cast<T*>(reinterpret_cast<const T*>(a.o)) + g * a.o_sg + h * a.o_sh + (int64_t)(q0 + r) * a.o_sr + 4 * hh;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                u32x2 pk;
-                pk.x = pack2<T>(o[dt][qd * 4 + 0] * inv, o[dt][qd * 4 + 1] * inv);
-                pk.y = pack2<T>(o[dt][qd * 4 + 2] * inv, o[dt][qd * 4 + 3] * inv);
-                *reinterpret_cast<u32x2*>(op + dt * 32 + 8 * qd) = pk;
-            }
+        store_out<T>(o, const_cast<T*>(reinterpret_cast<const T*>(a.o)) + g * a.o_sg + h * a.o_sh + (int64_t)(q0 + r) * a.o_sr + 4 * hh, inv);
         if (a.o32 != nullptr) store_f32(o, a.o32 + g * a.o_sg + h * a.o_sh + (int64_t)(q0 + r) * a.o_sr + 4 * hh, inv);
         if (hh == 0) a.lse[gh * a.Lq + q0 + r] = m_run + log2f(l_run);
     }
@@ -257,10 +175,9 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dq_kernel(const TAttnArgs a)
     __shared__ __attribute__((aligned(16))) char smem[4 * 4096];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t unit = (int64_t)blockIdx.x * 4 + wave;
-    if (unit >= (int64_t)a.G * a.H * a.nqt) return;
-    const int qt = (int)(unit % a.nqt);
-    const int64_t gh = unit / a.nqt;
+    int qt;
+    int64_t gh;
+    if (!wave_unit(wave, (int64_t)a.G * a.H * a.nqt, a.nqt, qt, gh)) return;
     const int h = (int)(gh % a.H);
     const int64_t g = gh / a.H;
     const int r = lane & 31, hh = lane >> 5;
@@ -304,7 +221,7 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dq_kernel(const TAttnArgs a)
     char* kl = smem + wave * 4096;
     int voff[2];
     tr_offsets(lane, voff);
-    const float sl = a.scale * kLog2eT;
+    const float sl = a.scale * kLog2e;
     const float keep = a.p_drop > 0.f ? 1.0f / (1.0f - a.p_drop) : 1.0f, ikeep = 1.0f - a.p_drop;
     const uint32_t rkey = drop_row_key(a.seed, (uint64_t)(gh * a.Lq + qrow)), thr = drop_threshold(a.p_drop);
 
@@ -337,7 +254,7 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dq_kernel(const TAttnArgs a)
                 const int key = key0 + acc_row(i, hh);
                 float c = nlse;
                 if constexpr (decltype(edge_c)::value) {
-                    if constexpr (MASKED) c = fmaf(fmaxf(mp[min(key, a.Lk - 1)], -2.0e38f), kLog2eT, nlse);
+                    if constexpr (MASKED) c = fmaf(fmaxf(mp[min(key, a.Lk - 1)], -2.0e38f), kLog2e, nlse);
                     c = key < a.Lk ? c : -INFINITY;
                 }
                 if (DROP && (i & 1) == 0) bits = drop_bits(rkey, key);
@@ -365,10 +282,9 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dkv_kernel(const TAttnArgs a
     __shared__ __attribute__((aligned(16))) char smem[4 * (2 * 4096 + 256)];   // per wave: a Q tile, a dO tile, the rows' statistics
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t unit = (int64_t)blockIdx.x * 4 + wave;
-    if (unit >= (int64_t)a.G * a.H * a.nkt) return;
-    const int kt = (int)(unit % a.nkt);
-    const int64_t gh = unit / a.nkt;
+    int kt;
+    int64_t gh;
+    if (!wave_unit(wave, (int64_t)a.G * a.H * a.nkt, a.nkt, kt, gh)) return;
     const int h = (int)(gh % a.H);
     const int64_t g = gh / a.H;
     const int r = lane & 31, hh = lane >> 5;
@@ -382,13 +298,13 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dkv_kernel(const TAttnArgs a
     frag_load<T>(reinterpret_cast<const T*>(a.k) + g * a.k_sg + h * a.k_sh + (int64_t)krow * a.k_sr + 8 * hh, kfb);
     frag_load<T>(reinterpret_cast<const T*>(a.v) + g * a.v_sg + h * a.v_sh + (int64_t)krow * a.v_sr + 8 * hh, vfb);
     float maskv = 0.f;
-    if constexpr (MASKED) maskv = fmaxf(a.mask[g * a.Lk + krow], -2.0e38f) * kLog2eT;
+    if constexpr (MASKED) maskv = fmaxf(a.mask[g * a.Lk + krow], -2.0e38f) * kLog2e;
     char* ql = smem + wave * (2 * 4096 + 256);
     char* dl = ql + 4096;
     float* stat = reinterpret_cast<float*>(dl + 4096);          // [0, 32): -LSE of the tile's rows, [32, 64): their D
     int voff[2];
     tr_offsets(lane, voff);
-    const float sl = a.scale * kLog2eT;
+    const float sl = a.scale * kLog2e;
     const float keep = a.p_drop > 0.f ? 1.0f / (1.0f - a.p_drop) : 1.0f, ikeep = 1.0f - a.p_drop;
     const float* stp = (hh == 0 ? a.lse : a.dsum) + gh * a.Lq;
     auto stat_load = [&](int q0) -> float {
@@ -441,7 +357,7 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dkv_kernel(const TAttnArgs a
             const float nli = (i & 3) == 0 ? nl[i >> 2].x : (i & 3) == 1 ? nl[i >> 2].y : (i & 3) == 2 ? nl[i >> 2].z : nl[i >> 2].w;
             const float dsi = (i & 3) == 0 ? dsv[i >> 2].x : (i & 3) == 1 ? dsv[i >> 2].y : (i & 3) == 2 ? dsv[i >> 2].z : dsv[i >> 2].w;
             bool kept = true;
-            if constexpr (DROP) kept = kept16(hash32((rkq + (uint32_t)((i & 3) + 8 * (i >> 2)) * kDropWeyl) ^ kj), kshift, thr);
+            if constexpr (DROP) kept = kept16(hash32((rkq + (uint32_t)acc_row(i, 0) * kDropWeyl) ^ kj), kshift, thr);
             const Adj ad = adjoint<T, DROP>(s[i], dp[i], sl, MASKED ? maskv + nli : nli, dsi, keep, ikeep, kept);
             pdf[i >> 3][i & 7] = static_cast<T>(ad.pd);
             dsf[i >> 3][i & 7] = static_cast<T>(ad.ds);

@@ -397,20 +397,29 @@ def attention_split8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: f
     assert k.shape == (b1, b0, lk, d) and v.shape == k.shape and d % 64 == 0
     assert q.dtype == k.dtype == v.dtype == torch.float32 and q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1
     out = torch.empty((b1, b0, lq, 4 * d), dtype=torch.uint8, device=q.device)
+    _attention_launch("cir_attention_split8", q, k, v, mask, (), out, (float(scale),))
+    return Split8Operand(out, d)
+
+
+def _attention_launch(entry: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask: Optional[torch.Tensor], extra: tuple, out: torch.Tensor,
+                      tail: tuple):
+    """The mask strides, the call and the PROFILE_ATTN record that `attention` and `attention_split8` share (include/cirrank.h: q, k, v views,
+    mask, *extra, out view, B1, B0, H, Lq, Lk, *tail, stream)."""
+    b1, b0, lq, d = q.shape
+    lk = k.shape[2]
     ms1 = ms0 = 0
     if mask is not None:
         assert mask.dtype == torch.float32 and mask.shape == (b1, b0, lk) and mask.stride(2) == 1
         ms1, ms0 = mask.stride(0), mask.stride(1)
     ev = _events() if PROFILE_ATTN is not None else None
-    code = _lib.load().cir_attention_split8(
+    code = getattr(_lib.load(), entry)(
         q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
-        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), _ptr(mask), ms1, ms0,
-        out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), b1, b0, d // 64, lq, lk, float(scale), _stream())
+        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), _ptr(mask), ms1, ms0, *extra,
+        out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), b1, b0, d // 64, lq, lk, *tail, _stream())
     if ev is not None:
         ev[1].record()
         PROFILE_ATTN.append((4.0 * b1 * b0 * lq * lk * d, *ev, (lq, lk)))
-    _lib.check(code, "cir_attention_split8")
-    return Split8Operand(out, d)
+    _lib.check(code, entry)
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, scale: float,
@@ -428,19 +437,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     assert d % 64 == 0 and v.shape == k.shape and out.shape == q.shape
     assert q.stride(3) == 1 and k.stride(3) == 1 and v.stride(3) == 1 and out.stride(3) == 1
     assert q.dtype == k.dtype == v.dtype == out.dtype
-    ms1 = ms0 = 0
-    if mask is not None:
-        assert mask.dtype == torch.float32 and mask.shape == (b1, b0, lk) and mask.stride(2) == 1
-        ms1, ms0 = mask.stride(0), mask.stride(1)
-    ev = _events() if PROFILE_ATTN is not None else None
-    code = _lib.load().cir_attention(
-        q.data_ptr(), q.stride(0), q.stride(1), q.stride(2), k.data_ptr(), k.stride(0), k.stride(1), k.stride(2),
-        v.data_ptr(), v.stride(0), v.stride(1), v.stride(2), _ptr(mask), ms1, ms0, _ptr(kv_index),
-        out.data_ptr(), out.stride(0), out.stride(1), out.stride(2), b1, b0, d // 64, lq, lk, float(scale), _DT[q.dtype], _stream())
-    if ev is not None:
-        ev[1].record()
-        PROFILE_ATTN.append((4.0 * b1 * b0 * lq * lk * d, *ev, (lq, lk)))
-    _lib.check(code, "cir_attention")
+    _attention_launch("cir_attention", q, k, v, mask, (_ptr(kv_index),), out, (float(scale), _DT[q.dtype]))
     return out
 
 
