@@ -120,6 +120,8 @@ class _EngineHost(nn.Module):
                                                # everywhere) - `set_text_stream32_from`
         self.long_caption_fold = False         # two-branch encoder: captions of 33-64 tokens take the long-caption query-side fold instead of the
                                                # projected K|V path (`set_long_caption_fold`; off by default)
+        self.long_caption_fold_wide = False    # two-branch encoder: captions of 33-64 tokens against 225-608 image tokens (384 px) take the key-split
+                                               # query-side fold instead of the projected K|V path (`set_long_caption_fold_wide`; off by default)
         self.short_caption_fold = False        # two-branch encoder: captions of at most 16 tokens take the one-block query-side fold instead of the
                                                # 32-token kernels (`set_short_caption_fold`; off by default)
         self.graph_candidates = 0              # `score` calls with at most this many candidate rows replay a captured HIP graph per
@@ -301,6 +303,7 @@ class BLIP_NLVR(_EngineHost):
         e.stream32_from = self.text_stream32_from
         e.fold_long = self.long_caption_fold
         e.fold_short = self.short_caption_fold
+        e.fold_long_wide = self.long_caption_fold_wide
         return e
 
     def set_long_caption_fold(self, on: bool = True):
@@ -311,6 +314,17 @@ class BLIP_NLVR(_EngineHost):
         self.long_caption_fold = bool(on)
         if self._engines is not None:
             self._engines[1].fold_long = self.long_caption_fold
+        return self
+
+    def set_long_caption_fold_wide(self, on: bool = True):
+        """Captions of 33-64 tokens against 225-608 image tokens (the reference's 384 px: 577 tokens, validate_stage2.py:327; captions are never
+        cut to 32 tokens, blip_stage2.py:113): run the cross-attention of fusion layers 0-10 through cir_cross_attention_folded_long_wide - the
+        keys of a head split over two waves - instead of the projected K|V path.  A switch of its own: `set_long_caption_fold` covers at most
+        224 image tokens and leaves this geometry projected.  Off by default (LABNOTES.md section 21); `NlvrEngine.fold_fallbacks` stays at 0
+        for such batches when it is on.  The setting lives on the model and is re-applied to every engine packed from it."""
+        self.long_caption_fold_wide = bool(on)
+        if self._engines is not None:
+            self._engines[1].fold_long_wide = self.long_caption_fold_wide
         return self
 
     def set_short_caption_fold(self, on: bool = True):

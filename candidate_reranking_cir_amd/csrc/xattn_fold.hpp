@@ -44,13 +44,14 @@ __device__ __forceinline__ typename Elem<T>::x8 pack_acc2(const f32x4& lo, const
 
 
 // The checks common to the folded entry points, in the order that decides which code a bad call gets, then the FoldArgs fill.  The caller
-// names its limits (max_l tokens, max_n keys) and the workgroup count its grid must hold in 31 bits.
+// names its limits (max_l tokens, max_n keys; lower ones where another entry point owns the range below) and the workgroup count its grid
+// must hold in 31 bits.
 inline int fold_args(FoldArgs& a, const void* q, int64_t q_sb, int64_t q_rs, const void* x, int64_t x_s1, const void* wkt, const void* wvp, int64_t w_sb,
                      const float* bv, const float* key_mask, int64_t mask_stride, void* out, int64_t o_st, int64_t o_sr, int64_t o_sb, int T, int L, int N,
-                     int D, int H, float scale, int dtype, int max_l, int max_n, int64_t grid_bound) {
+                     int D, int H, float scale, int dtype, int max_l, int max_n, int64_t grid_bound, int min_l = 1, int min_n = 1) {
     CIR_CHECK_PTR(q); CIR_CHECK_PTR(x); CIR_CHECK_PTR(wkt); CIR_CHECK_PTR(wvp); CIR_CHECK_PTR(bv); CIR_CHECK_PTR(out);
     if (T <= 0 || L <= 0 || N <= 0) return CIR_EINVAL;
-    if (D != kFoldD || H != 12 || L > max_l || N > max_n) return CIR_ESHAPE;
+    if (D != kFoldD || H != 12 || L > max_l || N > max_n || L < min_l || N < min_n) return CIR_ESHAPE;
     if (dtype != CIR_BF16 && dtype != CIR_F16) return CIR_EDTYPE;
     if (!cir_aligned16(q) || !cir_aligned16(x) || !cir_aligned16(wkt) || !cir_aligned16(wvp) || !cir_aligned16(bv) || (reinterpret_cast<uintptr_t>(out) & 7) ||
         q_sb % 8 || q_rs % 8 || x_s1 % 8 || w_sb % 8 || o_st % 4 || o_sr % 4 || o_sb % 4)

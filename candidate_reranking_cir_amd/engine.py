@@ -314,7 +314,7 @@ class MedEngine:
 class LayerPlan(NamedTuple):
     """One fusion layer of a `Plan`."""
     cls_only: bool          # per-token work on the CLS rows only (the trimmed last layer)
-    cross: str              # cross-attention path: "cls_fold", "fold_short", "fold32", "fold_long", "projected" or "bank"
+    cross: str              # cross-attention path: "cls_fold", "fold_short", "fold32", "fold_long", "fold_long_wide", "projected" or "bank"
     sdt: torch.dtype        # residual-stream type the layer receives ...
     sdt_out: torch.dtype    # ... and the one its last LayerNorm writes (the next layer's)
 
@@ -342,7 +342,7 @@ class NlvrEngine:
     Layer 0's self-attention block is candidate-independent and runs once per QUERY.
 
     Which of these launches a call issues is decided in one place: `plan` maps the call's sizes and the live switches (plain attributes,
-    set between calls: `trim_last`, `kv_chunk`, `fold_cls_kv`, `fold_cross_kv`, `fold_long`, `fold_short`, `stream32_from`, `cls_fold`) to a `Plan` before
+    set between calls: `trim_last`, `kv_chunk`, `fold_cls_kv`, `fold_cross_kv`, `fold_long`, `fold_long_wide`, `fold_short`, `stream32_from`, `cls_fold`) to a `Plan` before
     the first launch; `forward` executes it and `forward_graphed` keys its captures with it.  A new host-side switch belongs in `plan`.
     """
 
@@ -374,6 +374,11 @@ class NlvrEngine:
         # fold16 at 577 keys and 19-28 % slower than the 224-key kernel at 197 (LABNOTES.md section 18) - worth turning on for 384-px runs only
         # (BLIP_NLVR.set_short_caption_fold).
         self.fold_short = False
+        # Captions of 33 .. 64 tokens against 225 .. 608 keys (384 px: 577): with `fold_long_wide` on they take cir_cross_attention_folded_long_wide
+        # (four waves per head: two token halves x two key halves) instead of the projected path, and `fold_fallbacks` does not move.  A second
+        # switch: `fold_long` alone keeps sending this geometry to the projected path.  Off by default whatever it measures (LABNOTES.md
+        # section 21; BLIP_NLVR.set_long_caption_fold_wide).
+        self.fold_long_wide = False
         self.stream32_from = None    # layers >= this index keep their residual stream in fp32 (None: `stream_dtype` everywhere)
         self._graphs = {}            # graph_key -> ScoreGraph, in recency order (`forward_graphed`)
         e = prefix + "embeddings."
@@ -469,6 +474,8 @@ class NlvrEngine:
                 cross = "fold32"
             elif foldable and self.fold_long and 33 <= l <= 64 and n <= 224:
                 cross = "fold_long"
+            elif foldable and self.fold_long_wide and 33 <= l <= 64 and 225 <= n <= 608:
+                cross = "fold_long_wide"
             else:
                 cross = "projected" if bank is None else "bank"
             layers.append(LayerPlan(cls_only, cross, sd(i), sd(i + 1)))
@@ -564,8 +571,9 @@ class NlvrEngine:
         emask = None if emask2d is None else emask2d.view(t_n, 1, n).expand(t_n, 2, n)
         if lp.cross == "cls_fold":
             self._cross_cls_fold(qc, ccl, tok, rows)
-        elif lp.cross in ("fold_short", "fold32", "fold_long"):
-            fold = getattr(ops, {"fold_short": "cross_attention_folded_short", "fold32": "cross_attention_folded", "fold_long": "cross_attention_folded_long"}[lp.cross])
+        elif lp.cross in ("fold_short", "fold32", "fold_long", "fold_long_wide"):
+            fold = getattr(ops, {"fold_short": "cross_attention_folded_short", "fold32": "cross_attention_folded", "fold_long": "cross_attention_folded_long",
+                                 "fold_long_wide": "cross_attention_folded_long_wide"}[lp.cross])
             fold(qraw, tok, ly["wkt"], ly["wvp"], ly["bvf"], ccl, l, SCALE, heads=self.geo.num_attention_heads, mask=emask2d)
         elif lp.cross == "projected":
             self._cross_projected(ly, qc, ccl, tok, emask, kv_chunk)
@@ -638,7 +646,8 @@ class NlvrEngine:
         if plan.fallback and self.fold_fallbacks == 1:
             warnings.warn(f"captions of {l} tokens (> 32): the cross-attention runs the projected K|V path for this batch (~8 % of a step slower than "
                           "the query-side fold at 224 px); NlvrEngine.fold_fallbacks counts such calls; 33-64 tokens against <= 224 keys can take the "
-                          "long-caption fold instead: BLIP_NLVR.set_long_caption_fold()", stacklevel=3)
+                          "long-caption fold instead: BLIP_NLVR.set_long_caption_fold(); against 225-608 keys (384 px) its key-split form: "
+                          "BLIP_NLVR.set_long_caption_fold_wide()", stacklevel=3)
         emask2d = additive_encoder_mask(cand_mask).view(t_n, n) if cand_mask is not None else None       # (T, N): the folded kernels' form
         cc = torch.empty((t_n, l, 2, d), dtype=self.xdtype, device=z_t32.device)
         h32 = h16 = None

@@ -524,6 +524,13 @@ def cross_attention_folded_short(q: torch.Tensor, x: torch.Tensor, wkt: torch.Te
     return _cross_attention_folded("cir_cross_attention_folded_short", q, x, wkt, wvp, bv, out, l, scale, heads, mask)
 
 
+def cross_attention_folded_long_wide(q: torch.Tensor, x: torch.Tensor, wkt: torch.Tensor, wvp: torch.Tensor, bv: torch.Tensor, out: torch.Tensor, l: int,
+                                     scale: float, heads: int = 12, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cross_attention_folded for captions of 33 .. 64 tokens against 225 .. 608 keys (cir_cross_attention_folded_long_wide): the same operands
+    and packed weights; the keys of a head are summed in two halves by two waves."""
+    return _cross_attention_folded("cir_cross_attention_folded_long_wide", q, x, wkt, wvp, bv, out, l, scale, heads, mask)
+
+
 def embed_layernorm(ids: torch.Tensor, word: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
                     eps: float, dtype16: torch.dtype = torch.bfloat16, stream_dtype: torch.dtype = torch.float32):
     """BERT embeddings: LayerNorm(word[ids] + pos[:L]); ids (R, L) int64 -> (y_stream, y16) of shape (R, L, cols)."""

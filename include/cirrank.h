@@ -268,6 +268,21 @@ int cir_cross_attention_folded_short(const void* q, int64_t q_sb, int64_t q_rs, 
                                      int T, int L, int N, int D, int H, float scale, int dtype, void* stream);
 
 /*
+ * cir_cross_attention_folded_long at the reference's 384-px geometry (csrc/xattn_fold_units.hip; additive within ABI v15): the same operator
+ * (nlvr_encoder.py:150-168, 183-217), the same operands, packed weights, key mask and strides, for captions of more than 32 tokens
+ * (blip_stage2.py:113: padding='longest', no max_length) against the 577 image tokens of 384 px (validate_stage2.py:327).  D = 768, H = 12,
+ * 33 <= L <= 64, 225 <= N <= 608 (CIR_ESHAPE otherwise: cir_cross_attention_folded_long below 225 keys, cir_cross_attention_folded up to 32
+ * tokens, cir_gemm_bias_act + cir_attention beyond).  Four waves per head: two 32-token halves x two KEY halves (16-key blocks 0-19 and 20-39 of a
+ * 640-key capacity); one instantiation for every L, so a row's result does not depend on T, on the candidate's place in the batch, on L or
+ * on the wave that held it.  Summation order of a row: 32-feature units in order; key blocks in order within a half; half 0 + half 1 (row
+ * sums and contexts alike; both halves form the probabilities against the row's common maximum).  The key sum has two parts: rows are not
+ * bit-identical to cir_cross_attention_folded's.
+ */
+int cir_cross_attention_folded_long_wide(const void* q, int64_t q_sb, int64_t q_rs, const void* x, int64_t x_s1, const void* wkt, const void* wvp, int64_t w_sb,
+                                         const float* bv, const float* key_mask, int64_t mask_stride, void* out, int64_t o_st, int64_t o_sr, int64_t o_sb,
+                                         int T, int L, int N, int D, int H, float scale, int dtype, void* stream);
+
+/*
  * BertEmbeddings.forward (nlvr_encoder.py:68-91, med.py:87-110):
  *   y[r] = LayerNorm(word[ids[r]] + pos[r % L]) for r < rows; fp32 tables, outputs as cir_layernorm
  *   (y_stream in CIR_F32 / CIR_F16, y16 in dtype16).

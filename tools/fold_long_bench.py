@@ -1,6 +1,7 @@
 """Long-caption query-side fold (cir_cross_attention_folded_long, 33-64 caption tokens) against the projected path (K|V GEMM + cir_attention)
 on the same tensors; with `--fold short`, the one-block fold for captions of at most 16 tokens (cir_cross_attention_folded_short) against the
-32-token kernels (cir_cross_attention_folded) on the same tensors.  GPU box only.
+32-token kernels (cir_cross_attention_folded) on the same tensors; with `--fold wide`, the key-split fold for 33-64 caption tokens against
+225-608 keys (cir_cross_attention_folded_long_wide) against the projected path.  GPU box only.
 
   python tools/fold_long_bench.py                       one fusion layer: L in {33, 40, 48, 49, 64}, N = 197, T = 6720, fp16 and bf16
   python tools/fold_long_bench.py --mode step --tokens 40
@@ -9,12 +10,15 @@ on the same tensors; with `--fold short`, the one-block fold for captions of at 
   python tools/fold_long_bench.py --fold short          one fusion layer: L in {8, 12, 16} at (N, T) = (197, 6720) and (577, 1680), fp16 and bf16
   python tools/fold_long_bench.py --fold short --mode step --tokens 12 [--px 384 --queries 16]
                                                         the scoring step with BLIP_NLVR.set_short_caption_fold on and off
-  options: --t T  --n N  --lengths 33,40,..  --dtypes fp16,bf16  --rounds R  --px 224|384  --json out.json
+  python tools/fold_long_bench.py --fold wide           one fusion layer: L in {33, 40, 48, 49, 56, 64}, N = 577, T = 1680, fp16 and bf16
+  python tools/fold_long_bench.py --fold wide --mode step --tokens 40 [--queries 16]
+                                                        the 384-px scoring step with BLIP_NLVR.set_long_caption_fold_wide on and off
+  options: --t T  --n N (= --keys N)  --lengths 33,40,..  --dtypes fp16,bf16  --rounds R  --px 224|384  --json out.json
 
 Method: every shape is launched before it is timed and the part is warmed for 1.5 s on the work it is about to time; the two forms ALTERNATE
 inside a round (device events around `inner` back-to-back launches each), and the figure is the MEDIAN over the rounds, with the spread
 (min .. max) beside it.  Flops are the ones each form executes, computed from the shapes: the fold 2 T (2 H Lp 64 D + 2 H Lp D Np) with
-Lp = 16 ceil(L / 16) rows and Np = 224 keys as the kernel runs them, the projected path 2 T N D 4 D + 4 T 2 L N D; with `--fold short` both
+Lp = 16 ceil(L / 16) rows and Np = 224 keys as the kernel runs them (`--fold wide`: Lp = 64 rows and Np = 640 keys whatever L and N), the projected path 2 T N D 4 D + 4 T 2 L N D; with `--fold short` both
 forms are folds: Lp = 16 rows against 32, Np = 224 keys up to 224 and 608 above."""
 import argparse
 import json
@@ -79,8 +83,10 @@ def layer_mode(a):
             out = torch.empty((t_n, l, 2, D), dtype=dt, device="cuda")
             o2 = torch.empty((t_n, l, 2, D), dtype=dt, device="cuda")
 
+            fold = ops.cross_attention_folded_long_wide if a.fold == "wide" else ops.cross_attention_folded_long
+
             def folded():
-                ops.cross_attention_folded_long(q, x, wkt, wvp, bv, out, l, 0.125)
+                fold(q, x, wkt, wvp, bv, out, l, 0.125)
 
             def projected():
                 kv = ops.gemm(x.view(t_n * n, D), wkv, bkv).view(t_n, n, 4, D)
@@ -89,8 +95,8 @@ def layer_mode(a):
 
             ms = _alternate({"folded_long": folded, "projected": projected}, a.rounds, a.inner)
             (tf, tf0, tf1), (tp, tp0, tp1) = _stat(ms["folded_long"]), _stat(ms["projected"])
-            lp = 16 * -(-l // 16)
-            fl_f = 2.0 * t_n * 2 * (2 * H * lp * 64 * D + 2 * H * lp * D * 224)
+            lp, np_ = (64, 640) if a.fold == "wide" else (16 * -(-l // 16), 224)
+            fl_f = 2.0 * t_n * 2 * (2 * H * lp * 64 * D + 2 * H * lp * D * np_)
             fl_p = 2.0 * t_n * n * D * 4 * D + 4.0 * t_n * 2 * l * n * D
             diff = (out.float() - o2.float()).abs().max().item()
             print(f"{dname} T {t_n} L {l} N {n}: folded_long {tf * 1e3:.0f} us [{tf0 * 1e3:.0f} .. {tf1 * 1e3:.0f}] ({fl_f / tf / 1e9:.0f} TFLOP/s of its "
@@ -101,7 +107,7 @@ def layer_mode(a):
                              folded_long_mflop_per_candidate=round(fl_f / 1e6 / t_n, 1), projected_mflop_per_candidate=round(fl_p / 1e6 / t_n, 1),
                              folded_long_tflops=round(fl_f / tf / 1e9, 1), projected_tflops=round(fl_p / tp / 1e9, 1), max_abs_diff=diff))
             del q, out, o2
-    return dict(mode="layer", rounds=a.rounds, inner=a.inner, rows=rows)
+    return dict(mode="layer", fold=a.fold, rounds=a.rounds, inner=a.inner, rows=rows)
 
 
 def short_layer_mode(a):
@@ -158,7 +164,7 @@ def step_mode(a):
     import warnings
     warnings.simplefilter("ignore")                             # (the switch-off form reports its projected path once)
 
-    switch = m2.set_long_caption_fold if a.fold == "long" else m2.set_short_caption_fold
+    switch = {"long": m2.set_long_caption_fold, "wide": m2.set_long_caption_fold_wide, "short": m2.set_short_caption_fold}[a.fold]
 
     def form(on):
         def run():
@@ -181,26 +187,30 @@ def step_mode(a):
 if __name__ == "__main__":
     p = argparse.ArgumentParser()
     p.add_argument("--mode", choices=["layer", "step"], default="layer")
-    p.add_argument("--fold", choices=["long", "short"], default="long")
-    p.add_argument("--px", type=int, choices=[224, 384], default=224)
+    p.add_argument("--fold", choices=["long", "short", "wide"], default="long")
+    p.add_argument("--px", type=int, choices=[224, 384], default=None)
     p.add_argument("--t", type=int, default=None)
-    p.add_argument("--n", type=int, default=None)
+    p.add_argument("--n", "--keys", dest="n", type=int, default=None)
     p.add_argument("--lengths", default=None)
     p.add_argument("--dtypes", default="fp16,bf16")
     p.add_argument("--rounds", type=int, default=7)
     p.add_argument("--inner", type=int, default=5)
     p.add_argument("--tokens", type=int, default=None)
-    p.add_argument("--queries", type=int, default=64)
+    p.add_argument("--queries", type=int, default=None)
     p.add_argument("--k", type=int, default=105)
     p.add_argument("--json", default=None)
     args = p.parse_args()
     if not torch.cuda.is_available():
         sys.exit("fold_long_bench.py measures on an MI355X: no GPU found")
     if args.tokens is None:
-        args.tokens = 40 if args.fold == "long" else 12
+        args.tokens = 12 if args.fold == "short" else 40
+    args.px = args.px or (384 if args.fold == "wide" else 224)
+    args.queries = args.queries or (16 if args.fold == "wide" else 64)         # (384 px: 16 x 105 = 1680 candidates)
     if args.fold == "long":
         args.t, args.n, args.lengths = args.t or 6720, args.n or 197, args.lengths or "33,40,48,49,64"
-    res = step_mode(args) if args.mode == "step" else layer_mode(args) if args.fold == "long" else short_layer_mode(args)
+    if args.fold == "wide":
+        args.t, args.n, args.lengths = args.t or 1680, args.n or 577, args.lengths or "33,40,48,49,56,64"
+    res = step_mode(args) if args.mode == "step" else short_layer_mode(args) if args.fold == "short" else layer_mode(args)
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
         with open(args.json, "w") as f:
