@@ -225,9 +225,14 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dq_kernel(const TAttnArgs a)
     const float keep = a.p_drop > 0.f ? 1.0f / (1.0f - a.p_drop) : 1.0f, ikeep = 1.0f - a.p_drop;
     const uint32_t rkey = drop_row_key(a.seed, (uint64_t)(gh * a.Lq + qrow)), thr = drop_threshold(a.p_drop);
 
-    f32x16 dq[2];
+    // The row sums of dS vanish in exact arithmetic, so dQ = sum_j dS_j (k_j - kappa) for ANY vector kappa; with 16-bit Pd and dS they
+    // are off by ~2^-9 |dS|, and sum_j dS_j k_j multiplies that residue by whatever offset the keys have in common (keys at 33 +- 0.4:
+    // dQ wrong by 3-5 % in bf16, tests/test_attn_profiles_gpu.py).  The residue e = sum_j dS16_j is therefore taken out again around the
+    // row's own centre of the keys, kappa = sum_j Pd16_j k_j / sum_j Pd16_j (pk / psum: one more product on the staged K tile).
+    f32x16 dq[2], pk[2];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) { dq[0][i] = 0.f; dq[1][i] = 0.f; }
+    for (int i = 0; i < 16; ++i) { dq[0][i] = 0.f; dq[1][i] = 0.f; pk[0][i] = 0.f; pk[1][i] = 0.f; }
+    float esum = 0.f, psum = 0.f;
     X8 kf[4], vf[4], kr[4];
     frag_load<T>(kb + (int64_t)min(r, a.Lk - 1) * a.k_sr + 8 * hh, kf);
     frag_load<T>(vb + (int64_t)min(r, a.Lk - 1) * a.v_sr + 8 * hh, vf);
@@ -245,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dq_kernel(const TAttnArgs a)
             frag_load<T>(vb + (int64_t)min(key0 + 32 + r, a.Lk - 1) * a.v_sr + 8 * hh, vf);
             tile_load<T>(kb, a.k_sr, key0 + 32, a.Lk, lane, kr);
         }
-        X8 dsf[2];
+        X8 dsf[2], pdf[2];
         const bool edge = MASKED || key0 + 32 > a.Lk;              // only the last key tile can hold keys past Lk
         auto elements = [&](auto edge_c) {
             uint32_t bits = 0;
@@ -259,15 +264,25 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dq_kernel(const TAttnArgs a)
                 }
                 if (DROP && (i & 1) == 0) bits = drop_bits(rkey, key);
                 const Adj ad = adjoint<T, DROP>(s[i], dp[i], sl, c, dsum, keep, ikeep, DROP ? kept16(bits, (i & 1) * 16, thr) : true);
-                dsf[i >> 3][i & 7] = static_cast<T>(ad.ds);
+                const T ds16 = static_cast<T>(ad.ds);
+                dsf[i >> 3][i & 7] = ds16;
+                pdf[i >> 3][i & 7] = static_cast<T>(ad.pd);        // (exact: pd is a 16-bit value)
+                esum += static_cast<float>(ds16);
+                psum += ad.pd;
             }
         };
         if (edge) elements(std::true_type{}); else elements(std::false_type{});
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         tr_accumulate<T>(dq, kl, voff, dsf);                    // dQ^T[dh][q] += K^T[dh][key] (dS / scale)^T[key][q]
+        tr_accumulate<T>(pk, kl, voff, pdf);                    // Pd16 K: the centre of the keys, times psum
         __builtin_amdgcn_wave_barrier();
     }
+    esum += __shfl_xor(esum, 32, 64);
+    psum += __shfl_xor(psum, 32, 64);
+    const float corr = psum > 0.f ? esum / psum : 0.f;          // (a row whose every element was dropped has no centre: dS = 0 there)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { dq[0][i] = fmaf(-corr, pk[0][i], dq[0][i]); dq[1][i] = fmaf(-corr, pk[1][i], dq[1][i]); }
     if (qvalid) store_grad<T>(dq, a.dq, g * a.dq_sg + h * a.dq_sh + (int64_t)(q0 + r) * a.dq_sr + 4 * hh, a.grad16, a.scale);
 }
 
