@@ -7,6 +7,7 @@ uses this model's own ViT and the 256-d `vision_proj` / `text_proj` heads (blip_
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 from typing import Optional, Union
 
@@ -33,7 +34,10 @@ class BLIP_Retrieval(_EngineHost):
                  vit: str = "base", vit_grad_ckpt: bool = False, vit_ckpt_layer: int = 0, embed_dim: int = 256, *,
                  vit_geometry: Optional[VitGeometry] = None, tokenizer=None):
         super().__init__()
-        self.vit_geometry = vit_geometry or VitGeometry.named(vit, image_size)
+        # blip_stage1.py:34 passes create_vit no drop_path_rate: the stage-I image encoder has no DropPath (the stage-II one has 0.1) - a
+        # copy, so that a geometry object shared with a stage-II model keeps its rate
+        self.vit_geometry = dataclasses.replace(vit_geometry or VitGeometry.named(vit, image_size), drop_path_rate=0.0)
+        self.image_tuning = False              # `set_image_tuning`: image features with a graph in .train() mode (--blip-img-tune); off by default
         self.bert_geometry = load_bert_geometry(med_config)
         self.bert_geometry.encoder_width = self.vit_geometry.width
         self.tokenizer = tokenizer if tokenizer is not None else default_tokenizer()
@@ -58,9 +62,49 @@ class BLIP_Retrieval(_EngineHost):
             self._packed_key = key
         return self._engines
 
-    @torch.no_grad()
+    def set_image_tuning(self, on: bool = True):
+        """Stage-I training with a trainable image encoder (stage1_train.py --blip-img-tune, :144-190 / :383-425).  On: in `.train()` mode
+        with grad enabled, `img_embed` returns tokens with a graph through the ViT (`train_vit.vit_train`) where a `visual_encoder.*`
+        parameter requires grad, its pooled features carry one into `vision_proj` (and the CLS row) through cir_pooled_head_fwd / _bwd, and
+        `img_txt_fusion(..., train=True)` accepts image features that require a gradient and hands it back (`train_stage1.MedTrainer`:
+        12 more dgrad GEMMs of B * N rows).  Off (the default): `img_embed` runs under no_grad and such inputs are refused, as before.  In
+        `.eval()`, under no_grad or with a fully frozen image side the switch changes nothing.  The setting is a plain attribute of the
+        model: it survives `.to()` and `.train()` / `.eval()`."""
+        self.image_tuning = bool(on)
+        return self
+
+    def _image_side_trained(self, pooled: bool):
+        """(ViT trained, pooled head trained) for an `img_embed` call that builds a graph; (False, False) otherwise."""
+        if not (self.image_tuning and self.training and torch.is_grad_enabled()):
+            return False, False
+        vit = any(p.requires_grad for n, p in self.named_parameters() if n.startswith("visual_encoder."))
+        head = pooled and (vit or self.vision_proj.weight.requires_grad or self.vision_proj.bias.requires_grad)
+        return vit, head
+
     def img_embed(self, image, atts=False, return_pool_and_normalized=False):
-        """blip_stage1.py:48-65: ViT tokens (B, N, D) fp32 [, normalised 256-d pooled features][, ones mask]."""
+        """blip_stage1.py:48-65: ViT tokens (B, N, D) fp32 [, normalised 256-d pooled features][, ones mask].  Without a graph, unless
+        `set_image_tuning()` is on (see there)."""
+        vit_on, head_on = self._image_side_trained(return_pool_and_normalized)
+        if not (vit_on or head_on):
+            return self._img_embed_frozen(image, atts, return_pool_and_normalized)
+        if self.device.type != "cuda":
+            raise RuntimeError("BLIP_Retrieval runs on an MI355X only: move the model to 'cuda' (no CPU path)")
+        if vit_on:
+            from .train_vit import vit_train
+            y32 = vit_train(self, image)                                             # tokens with a graph (no DropPath: rate 0 here)
+        else:
+            with torch.no_grad():
+                y32, _ = self.engines()[1].forward(image.to(self.device), want32=True)
+        out = (y32,)
+        if return_pool_and_normalized:
+            from .train_stage1 import pooled_head_train
+            out += (pooled_head_train(y32, self.vision_proj.weight, self.vision_proj.bias),)
+        if atts:
+            out += (torch.ones(y32.shape[:-1], dtype=torch.long, device=y32.device),)
+        return out[0] if len(out) == 1 else out
+
+    @torch.no_grad()
+    def _img_embed_frozen(self, image, atts=False, return_pool_and_normalized=False):
         _, vit, heads = self.engines()
         y32, _ = vit.forward(image.to(self.device), want32=True)
         out = (y32,)
@@ -109,7 +153,8 @@ class BLIP_Retrieval(_EngineHost):
         `F.normalize(text_proj(z_t[:, 0]))` used by stage-I retrieval.  train=True: logits = that feature @ t_image_embeds^T / temp (B, Bt),
         t_image_embeds the normalised pooled target features (B, 256).  In .train() mode with grad enabled that is the stage-I training step
         (stage1_train.py:170-172): the logits are differentiable w.r.t. the encoder layers, embeddings, text_proj and temp
-        (train_stage1.MedTrainer); in .eval() mode or under no_grad the same head runs on this mode's z_t, without a graph."""
+        (train_stage1.MedTrainer); in .eval() mode or under no_grad the same head runs on this mode's z_t, without a graph.  Image
+        features that require a gradient are refused unless `set_image_tuning()` is on; then their gradients are returned as well."""
         if not train:
             with torch.no_grad():
                 ids, mask = encode_text(self.tokenizer, text, self.device)          # blip_stage1.py:72-73
@@ -120,7 +165,8 @@ class BLIP_Retrieval(_EngineHost):
                 return ops.l2_normalize(ops.linear_f32(z.last_hidden_state[:, 0, :], heads["tw"], heads["tb"]))
         from . import train_ops as T
         from .train_stage1 import _refuse_image_grads, stage1_train
-        _refuse_image_grads(r_image_embeds, t_image_embeds)
+        if not self.image_tuning:
+            _refuse_image_grads(r_image_embeds, t_image_embeds)
         ids, mask = encode_text(self.tokenizer, text, self.device)
         if self.training and torch.is_grad_enabled():
             return stage1_train(self, r_image_embeds, t_image_embeds, ids, mask)

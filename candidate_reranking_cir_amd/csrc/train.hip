@@ -813,6 +813,110 @@ __global__ __launch_bounds__(256) void head_sums_kernel(const float* __restrict_
     }
 }
 
+// ---- image side of the stage-I step when the image encoder is trained (stage1_train.py --blip-img-tune): the gradient of the logits
+// w.r.t. the target features, and the pooled head F.normalize(vision_proj(tokens[:, 0])) (blip_stage1.py:57) with its adjoint.  Same
+// conventions as the head above: fp32 FMA chains, fixed-order reductions, no atomics.
+constexpr int kPoolMaxD = 2048;
+
+// dtarget[j][:] = (1 / temp) sum_i dlogits[i][j] p_hat[i][:] (the adjoint of blip_stage1.py:91 w.r.t. target_features): one block per
+// target row j, the query rows i in order
+__global__ __launch_bounds__(256) void contrastive_bwd_target_kernel(const float* __restrict__ dlogits, const float* __restrict__ p_hat,
+                                                                     const float* __restrict__ temp, float* __restrict__ dtarget,
+                                                                     int B, int Bt, int E) {
+    const int64_t j = blockIdx.x;
+    const int t = threadIdx.x;
+    float acc[kHeadMaxE / 256];
+#pragma unroll
+    for (int c = 0; c < kHeadMaxE / 256; ++c) acc[c] = 0.f;
+    for (int64_t i = 0; i < B; ++i) {
+        const float g = dlogits[i * Bt + j];
+        const float* pr = p_hat + i * E;
+#pragma unroll
+        for (int c = 0; c < kHeadMaxE / 256; ++c) {
+            const int e = t + 256 * c;
+            if (e < E) acc[c] = fmaf(g, pr[e], acc[c]);
+        }
+    }
+    const float tp = temp[0];
+#pragma unroll
+    for (int c = 0; c < kHeadMaxE / 256; ++c) {
+        const int e = t + 256 * c;
+        if (e < E) dtarget[j * E + e] = acc[c] / tp;
+    }
+}
+
+// one block per image i: t = x_i W^T + b with the k-ordered FMA chain of linear_f32_kernel (misc.hip: acc from 0 over k = 0 .. D - 1, then
+// + bias), the norm with l2_normalize_kernel's one-wave order (lane-strided FMA sums, the wave butterfly), t_hat = t * inv - so t_hat has the
+// bits of cir_l2_normalize(cir_linear_f32(...)).  x_i = the CLS row of image i, read in place at row stride ldx
+__global__ __launch_bounds__(256) void pooled_head_fwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ W,
+                                                              const float* __restrict__ bias, float* __restrict__ t_hat,
+                                                              float* __restrict__ inv_norm, int E, int D) {
+    __shared__ __attribute__((aligned(16))) float xs[kPoolMaxD];
+    __shared__ float ts[kHeadMaxE];
+    __shared__ float inv_s;
+    const int64_t i = blockIdx.x;
+    const int t = threadIdx.x;
+    for (int d = t; d < D; d += 256) xs[d] = x[i * ldx + d];
+    __syncthreads();
+    for (int e = t; e < E; e += 256) {
+        const float4* wr = reinterpret_cast<const float4*>(W + (int64_t)e * D);
+        float acc = 0.f;
+        for (int d4 = 0; d4 < D / 4; ++d4) {
+            const float4 w = wr[d4];
+            const float4 a = *reinterpret_cast<const float4*>(xs + 4 * d4);
+            acc = fmaf(a.x, w.x, acc);
+            acc = fmaf(a.y, w.y, acc);
+            acc = fmaf(a.z, w.z, acc);
+            acc = fmaf(a.w, w.w, acc);
+        }
+        ts[e] = acc + bias[e];
+    }
+    __syncthreads();
+    if (t < 64) {
+        float s = 0.f;
+        for (int c = t; c < E; c += 64) { const float v = ts[c]; s = fmaf(v, v, s); }
+        const float inv = 1.0f / fmaxf(sqrtf(wave_sum(s)), 1e-12f);          // F.normalize: x / max(||x||, eps)
+        if (t == 0) { inv_s = inv; inv_norm[i] = inv; }
+    }
+    __syncthreads();
+    const float inv = inv_s;
+    for (int e = t; e < E; e += 256) t_hat[i * E + e] = ts[e] * inv;
+}
+
+// normalise adjoint, one block per image i: dt = inv (dt_hat - t_hat (t_hat . dt_hat)); a row clamped by the epsilon (inv = 1e12) gets
+// dt = inv dt_hat, F.normalize's own gradient there (the clamp is a constant divisor)
+__global__ __launch_bounds__(256) void pooled_head_bwd_rows_kernel(const float* __restrict__ dt_hat, const float* __restrict__ t_hat,
+                                                                   const float* __restrict__ inv_norm, float* __restrict__ dt, int E) {
+    __shared__ float red4[4];
+    const int64_t i = blockIdx.x;
+    const int t = threadIdx.x;
+    const float inv = inv_norm[i];
+    const bool clamped = inv >= 1.0f / 1e-12f;                                // the forward's value for ||t|| < eps
+    float s = 0.f;
+    for (int e = t; e < E; e += 256) s = fmaf(t_hat[i * E + e], dt_hat[i * E + e], s);
+    const float sum = block256_sum(s, red4);
+    const float sd = clamped ? 0.f : sum;
+    for (int e = t; e < E; e += 256) dt[i * E + e] = (dt_hat[i * E + e] - t_hat[i * E + e] * sd) * inv;
+}
+
+// vision_proj's gradients ADDED to dW / db (the blip_bs mini-batches of a step each contribute): dW[e][d] += sum_i dt[i][e] x[i][d],
+// db[e] += sum_i dt[i][e]; rows in order, one adder per element.  blockIdx.y = e; the last x-block column carries db
+__global__ __launch_bounds__(256) void pooled_head_wgrad_kernel(const float* __restrict__ dt, const float* __restrict__ x, int64_t ldx,
+                                                                float* __restrict__ dW, float* __restrict__ db, int B, int E, int D) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    const int64_t e = blockIdx.y;
+    if (d < D) {
+        float acc = 0.f;
+        for (int64_t i = 0; i < B; ++i) acc = fmaf(dt[i * E + e], x[i * ldx + d], acc);
+        dW[e * D + d] += acc;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        float acc = 0.f;
+        for (int64_t i = 0; i < B; ++i) acc += dt[i * E + e];
+        db[e] += acc;
+    }
+}
+
 }  // namespace cir
 
 using namespace cir;
@@ -1042,5 +1146,53 @@ extern "C" int cir_contrastive_bwd(const float* dlogits, const float* target, co
         hipLaunchKernelGGL(head_wgrad_kernel, dim3((D + 255) / 256, E), dim3(256), 0, s, dp, x, ldx, dW, B, E, D);
     }
     hipLaunchKernelGGL(head_sums_kernel, dim3(proj ? (E + 255) / 256 : 1), dim3(256), 0, s, dp, row_scratch, temp, proj ? db : nullptr, dtemp, B, E);
+    CIR_LAUNCH_RESULT();
+}
+
+extern "C" int cir_contrastive_bwd_target(const float* dlogits, const float* p_hat, const float* temp, float* dtarget, int B, int Bt, int E,
+                                          int dtype, void* stream) {
+    CIR_CHECK_PTR(dlogits); CIR_CHECK_PTR(p_hat); CIR_CHECK_PTR(temp); CIR_CHECK_PTR(dtarget);
+    if (B <= 0 || Bt <= 0 || E <= 0) return CIR_EINVAL;
+    if (dtype != CIR_F32) return CIR_EDTYPE;
+    if (E > kHeadMaxE || E % 4 != 0 || B > 65535 || Bt > 65535 || (int64_t)B * Bt >= (int64_t(1) << 31)) return CIR_ESHAPE;
+    if (!cir_aligned16(dlogits) || !cir_aligned16(p_hat) || !cir_aligned16(dtarget) || (reinterpret_cast<uintptr_t>(temp) & 3)) return CIR_EALIGN;
+    hipLaunchKernelGGL(contrastive_bwd_target_kernel, dim3(Bt), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dlogits, p_hat, temp, dtarget,
+                       B, Bt, E);
+    CIR_LAUNCH_RESULT();
+}
+
+static int pooled_head_shape(const float* x, int64_t ldx, int Bt, int E, int D) {
+    if (Bt <= 0 || E <= 0 || D <= 0) return CIR_EINVAL;
+    if (E > kHeadMaxE || E % 4 != 0 || D > kPoolMaxD || D % 4 != 0 || Bt > 65535 || ldx < D || (int64_t)(Bt - 1) * ldx + D >= (int64_t(1) << 40))
+        return CIR_ESHAPE;
+    return cir_rows_ok(x, ldx) ? CIR_OK : CIR_EALIGN;
+}
+
+extern "C" int cir_pooled_head_fwd(const float* x, int64_t ldx, const float* W, const float* bias, float* t_hat, float* inv_norm, int Bt, int E,
+                                   int D, int dtype, void* stream) {
+    CIR_CHECK_PTR(x); CIR_CHECK_PTR(W); CIR_CHECK_PTR(bias); CIR_CHECK_PTR(t_hat); CIR_CHECK_PTR(inv_norm);
+    if (dtype != CIR_F32) return CIR_EDTYPE;
+    const int rc = pooled_head_shape(x, ldx, Bt, E, D);
+    if (rc != CIR_OK) return rc;
+    if (!cir_aligned16(W) || !cir_aligned16(t_hat) || (reinterpret_cast<uintptr_t>(bias) & 3) || (reinterpret_cast<uintptr_t>(inv_norm) & 3)) return CIR_EALIGN;
+    hipLaunchKernelGGL(pooled_head_fwd_kernel, dim3(Bt), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, ldx, W, bias, t_hat, inv_norm, E, D);
+    CIR_LAUNCH_RESULT();
+}
+
+extern "C" int cir_pooled_head_bwd(const float* dt_hat, const float* t_hat, const float* inv_norm, const float* x, int64_t ldx, const float* W,
+                                   float* dt, float* dx, int64_t lddx, float* dW, float* db, int Bt, int E, int D, int dtype, void* stream) {
+    CIR_CHECK_PTR(dt_hat); CIR_CHECK_PTR(t_hat); CIR_CHECK_PTR(inv_norm); CIR_CHECK_PTR(x); CIR_CHECK_PTR(W); CIR_CHECK_PTR(dt);
+    CIR_CHECK_PTR(dW); CIR_CHECK_PTR(db);
+    if (dtype != CIR_F32) return CIR_EDTYPE;
+    const int rc = pooled_head_shape(x, ldx, Bt, E, D);
+    if (rc != CIR_OK) return rc;
+    if (dx != nullptr && (lddx < D || (int64_t)(Bt - 1) * lddx + D >= (int64_t(1) << 40))) return CIR_ESHAPE;
+    if (!cir_aligned16(dt_hat) || !cir_aligned16(t_hat) || !cir_aligned16(dt) || !cir_aligned16(W) || !cir_aligned16(dW) ||
+        (reinterpret_cast<uintptr_t>(db) & 3) || (reinterpret_cast<uintptr_t>(inv_norm) & 3) || (dx != nullptr && !cir_rows_ok(dx, lddx)))
+        return CIR_EALIGN;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(pooled_head_bwd_rows_kernel, dim3(Bt), dim3(256), 0, s, dt_hat, t_hat, inv_norm, dt, E);
+    if (dx != nullptr) hipLaunchKernelGGL(head_dgrad_kernel, dim3((D + 255) / 256, Bt), dim3(256), 0, s, dt, W, dx, lddx, E, D);
+    hipLaunchKernelGGL(pooled_head_wgrad_kernel, dim3((D + 255) / 256, E), dim3(256), 0, s, dt, x, ldx, dW, db, Bt, E, D);
     CIR_LAUNCH_RESULT();
 }

@@ -454,3 +454,55 @@ def contrastive_bwd(dlogits: torch.Tensor, target: torch.Tensor, temp: torch.Ten
                                                scratch.data_ptr(), dtemp.data_ptr(), _ptr(x), ldx, _ptr(w), _ptr(dx), lddx, _ptr(dw), _ptr(db), d, b, bt, e,
                                                _lib.CIR_F32, _stream()), "cir_contrastive_bwd")
     return dp
+
+
+def contrastive_bwd_target(dlogits: torch.Tensor, p_hat: torch.Tensor, temp: torch.Tensor) -> torch.Tensor:
+    """dtarget (Bt, E) = dlogits^T p_hat / temp (cir_contrastive_bwd_target; blip_stage1.py:91 w.r.t. target_features): dlogits (B, Bt),
+    p_hat (B, E) fp32 contiguous, temp read on the device.  Fixed order, bit-reproducible."""
+    _need_cuda(dlogits, p_hat, temp)
+    b, e = p_hat.shape
+    bt = dlogits.shape[1]
+    assert dlogits.shape == (b, bt) and dlogits.dtype == p_hat.dtype == temp.dtype == torch.float32 and dlogits.is_contiguous() and p_hat.is_contiguous()
+    out = torch.empty((bt, e), dtype=torch.float32, device=p_hat.device)
+    _lib.check(_lib.load().cir_contrastive_bwd_target(dlogits.data_ptr(), p_hat.data_ptr(), temp.data_ptr(), out.data_ptr(), b, bt, e, _lib.CIR_F32,
+                                                      _stream()), "cir_contrastive_bwd_target")
+    return out
+
+
+def _cls_rows(t: torch.Tensor):
+    """(Bt, D) rows with unit last stride (the CLS rows tokens[:, 0] of a (Bt, N, D) tensor, in place) -> (Bt, D, row stride)."""
+    assert t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1
+    return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def pooled_head_fwd(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor):
+    """(t_hat (Bt, E), inv_norm (Bt)) of F.normalize(x W^T + b) (cir_pooled_head_fwd, blip_stage1.py:57); x (Bt, D) rows at any row stride."""
+    _need_cuda(x, w, bias)
+    bt, d, ldx = _cls_rows(x)
+    e = w.shape[0]
+    assert w.shape == (e, d) and w.is_contiguous() and bias.shape == (e,) and bias.is_contiguous() and w.dtype == bias.dtype == torch.float32
+    t_hat = torch.empty((bt, e), dtype=torch.float32, device=x.device)
+    inv = torch.empty((bt,), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().cir_pooled_head_fwd(x.data_ptr(), ldx, w.data_ptr(), bias.data_ptr(), t_hat.data_ptr(), inv.data_ptr(), bt, e, d,
+                                               _lib.CIR_F32, _stream()), "cir_pooled_head_fwd")
+    return t_hat, inv
+
+
+def pooled_head_bwd(dt_hat: torch.Tensor, t_hat: torch.Tensor, inv_norm: torch.Tensor, x: torch.Tensor, w: torch.Tensor, dw: torch.Tensor,
+                    db: torch.Tensor, dx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adjoint of `pooled_head_fwd` (cir_pooled_head_bwd): returns dt (Bt, E); ADDS vision_proj's gradients to dw (E, D) / db (E); WRITES
+    dx (Bt, D) rows (any row stride: the CLS rows of a token-gradient tensor whose other rows the caller zeroed) when given."""
+    _need_cuda(dt_hat, t_hat, inv_norm, x, w, dw, db, dx)
+    bt, d, ldx = _cls_rows(x)
+    e = w.shape[0]
+    assert dt_hat.shape == t_hat.shape == (bt, e) and dt_hat.is_contiguous() and t_hat.is_contiguous() and dt_hat.dtype == t_hat.dtype == torch.float32
+    assert w.shape == dw.shape == (e, d) and w.is_contiguous() and dw.is_contiguous() and db.shape == (e,) and db.is_contiguous()
+    assert w.dtype == dw.dtype == db.dtype == inv_norm.dtype == torch.float32 and inv_norm.shape == (bt,)
+    lddx = 0
+    if dx is not None:
+        assert dx.shape == (bt, d)
+        lddx = _cls_rows(dx)[2]
+    dt = torch.empty_like(t_hat)
+    _lib.check(_lib.load().cir_pooled_head_bwd(dt_hat.data_ptr(), t_hat.data_ptr(), inv_norm.data_ptr(), x.data_ptr(), ldx, w.data_ptr(), dt.data_ptr(),
+                                               _ptr(dx), lddx, dw.data_ptr(), db.data_ptr(), bt, e, d, _lib.CIR_F32, _stream()), "cir_pooled_head_bwd")
+    return dt

@@ -15,7 +15,8 @@ dropout + residual + LayerNorm kernels and their adjoints, one grouped weight-gr
   - one attention group per query: the self-attention over its L caption rows with the key mask, the cross-attention of its L rows
     against the N tokens of ITS OWN reference image (no mask: the reference's image masks are all ones);
   - the cross K|V projection of all B * N reference tokens, cast to 16 bits once per step; its weight gradient contracts over B * N rows
-    (18x the text-side products' rows at N = 577) and is split by the grouped planner; no gradient flows into the image tokens;
+    (18x the text-side products' rows at N = 577) and is split by the grouped planner; no gradient flows into the image tokens unless
+    the model's `set_image_tuning()` switch is on and they require one (--blip-img-tune: `MedTrainer.backward`, `dinputs`);
   - the contrastive head on cir_contrastive_fwd / _bwd (fp32, fixed-order reductions: bit-reproducible), text_proj's forward on
     cir_linear_f32 reading the CLS rows of the fp32 stream in place and its adjoint inside cir_contrastive_bwd.
 Dropout: the six sites of train_med.MedDropoutForward with the same site seeds (`train_med.site_seed`) and element numbering, one base
@@ -82,8 +83,9 @@ class MedTrainer(Trainer):
     # ------------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, ref_tokens: torch.Tensor, target: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
-                seed=None) -> torch.Tensor:
-        """ref_tokens (B, N, Dv), target (Bt, E) normalised pooled features, ids / mask (B, L) with [ENC] set -> logits (B, Bt) fp32."""
+                seed=None, need_dref: bool = False, need_dtarget: bool = False) -> torch.Tensor:
+        """ref_tokens (B, N, Dv), target (Bt, E) normalised pooled features, ids / mask (B, L) with [ENC] set -> logits (B, Bt) fp32.
+        `need_dref` / `need_dtarget`: the backward of this forward also forms the gradients of the two image-side inputs (`dinputs`)."""
         g, dt = self.geo, self.dtype
         q_n, l = input_ids.shape
         n, dv = ref_tokens.shape[1], ref_tokens.shape[2]
@@ -103,7 +105,7 @@ class MedTrainer(Trainer):
         if pos is None or tuple(pos.shape) != (q_n, l):                             # position of every row (built once per batch shape)
             pos = self._pos_idx = torch.arange(l, device=dev).repeat(q_n, 1)
         pos = pos.view(-1)
-        self.sv = sv = {"ids": ids, "q_n": q_n, "l": l, "n": n, "seed": seed}
+        self.sv = sv = {"ids": ids, "q_n": q_n, "l": l, "n": n, "seed": seed, "need_dref": bool(need_dref), "need_dtarget": bool(need_dtarget)}
         # BertEmbeddings (med.py:87-108): LayerNorm(word + position), dropout
         pre_e = T.eltwise(ops.gather_rows(self.word, ids.view(-1), f32), T.MODE_ADD, ops.gather_rows(self.pos, pos, f32))
         h32, h16 = self.ln_e.fwd(pre_e, dt)
@@ -148,7 +150,11 @@ class MedTrainer(Trainer):
     # ------------------------------------------------------------------------------------------------ backward
     @torch.no_grad()
     def backward(self, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """dlogits (B, Bt) fp32 -> {parameter name: fp32 gradient} for the 319 trained tensors."""
+        """dlogits (B, Bt) fp32 -> {parameter name: fp32 gradient} for the 319 trained tensors.  Where the forward asked for them, the
+        gradients of the image-side inputs are left in `dinputs` = (d ref_tokens (B, N, Dv) | None, d target (Bt, E) | None), fp32 and
+        UNSCALED: d ref_tokens = sum over the layers of dkv16_l W_ckv,l - the cross K|V dgrad product of every layer, layers 11 -> 0, each
+        adding to the running fp32 sum in its GEMM epilogue (one adder per element, fixed order) -, d target from
+        cir_contrastive_bwd_target (blip_stage1.py:91)."""
         sv, g, dt, slab = self.sv, self.geo, self.dtype, self.slab
         det = slab.read_mode()                                                      # {} or the fixed-order forms' workspace (deterministic mode)
         dev = dlogits.device
@@ -165,6 +171,9 @@ class MedTrainer(Trainer):
         T.contrastive_bwd(dl, sv["target"], self.temp, sv["p_hat"], sv["inv"], slab.gflat[self._temp_off:self._temp_off + 1], x=sv["cls"], w=self.tp_w,
                           dx=dh.view(q_n, l * d)[:, :d], dw=slab.grad("text_proj.weight"), db=slab.grad("text_proj.bias"))
         enc16 = sv["enc16"]
+        need_dref = sv["need_dref"]
+        dtarget = T.contrastive_bwd_target(dl, sv["p_hat"], self.temp) if sv["need_dtarget"] else None
+        dref = None                                                                 # running sum over the layers (B N, Dv) fp32
         for i in reversed(range(len(self.layers))):
             ly, s = self.layers[i], sv["layers"][i]
             wq: list = []                                                           # this layer's weight gradients: ONE launch at its end
@@ -181,7 +190,10 @@ class MedTrainer(Trainer):
                                   self._heads(s["cx"], q_n, l), self._heads(dcx16, q_n, l), s["ca"], self._heads(dcq16, q_n, l),
                                   self._heads(dkv16, q_n, n, 0, 2), self._heads(dkv16, q_n, n, 1, 2), self._scale, pa,
                                   site_seed(seed, i, SITE_CROSS_ATTN), out32=self._heads(s["cx32"], q_n, l))
-            ly["ckv"].bwd16(enc16, dkv16, need_dx=False, bias=True, queue=wq)       # B N rows; no gradient into the (frozen) image tokens
+            if need_dref:                                                           # B N rows; dkv16 W_ckv joins the image tokens' gradient
+                dref = ly["ckv"].bwd16(enc16, dkv16, need_dx=True, bias=True, residual=dref, queue=wq)
+            else:                                                                   # no gradient into the (frozen) image tokens
+                ly["ckv"].bwd16(enc16, dkv16, need_dx=False, bias=True, queue=wq)
             da = ly["cq"].bwd16(s["a16"], dcq16, bias=True, residual=dpre2, queue=wq)
             dpre1, dt16 = ly["ln1"].bwd_res(s["pre1"], da, dt, dbias=ly["o"].db, p_drop=ph, seed=site_seed(seed, i, SITE_SELF_OUT))
             dctx16 = ly["o"].bwd16(s["ctx"], dt16, dx_dtype=dt, queue=wq)
@@ -194,6 +206,11 @@ class MedTrainer(Trainer):
             self._wgrad_grouped(wq)
         de = dh if ph <= 0 else T.eltwise(dh, T.MODE_DROPOUT, p_drop=ph, seed=site_seed(seed, 0, SITE_EMB))
         T.embed_bwd(sv["ids"].view(-1), self.ln_e.bwd(sv["pre_e"], de), self.dword, self.dpos, l, **det)
+        # the pass ran on grad_scale * dlogits (fp16 operands): the power of two is divided out of the input gradients as _finish_backward
+        # divides it out of the parameters' before they return to autograd
+        if self.grad_scale != 1.0:
+            dref, dtarget = (None if x is None else T.eltwise(x, T.MODE_SCALE, p_drop=1.0 / self.grad_scale) for x in (dref, dtarget))
+        self.dinputs = (None if dref is None else dref.view(q_n, n, -1), dtarget)
         self.sv = None                                                              # (the saved activations are released with the pass)
         return self._finish_backward()
 
@@ -205,7 +222,9 @@ class _Stage1TrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, trainer, ref_tokens, target, ids, mask):
         ctx.trainer = trainer
-        out = trainer.forward(ref_tokens, target, ids, mask)
+        need = ctx.needs_input_grad
+        ctx.in_meta = [(t.dtype, t.device, tuple(t.shape)) for t in (ref_tokens, target)]
+        out = trainer.forward(ref_tokens, target, ids, mask, need_dref=need[2], need_dtarget=need[3])
         trainer._claim(ctx)
         return out
 
@@ -214,7 +233,44 @@ class _Stage1TrainFn(torch.autograd.Function):
         tr = ctx.trainer
         tr._consume(ctx)
         _install_grads(tr, tr.backward(dlogits.contiguous().float()))
-        return None, None, None, None, None, None
+        dins, tr.dinputs = tr.dinputs, (None, None)
+        dins = [None if gq is None else gq.to(device=dev, dtype=dt).view(shape) for gq, (dt, dev, shape) in zip(dins, ctx.in_meta)]
+        return None, None, dins[0], dins[1], None, None
+
+
+class _PooledHeadFn(torch.autograd.Function):
+    """One autograd node around cir_pooled_head_fwd / _bwd: F.normalize(vision_proj(tokens[:, 0])) (blip_stage1.py:57).  The CLS rows are
+    read in place; the backward ADDS vision_proj's gradients into `.grad` directly (as the trainers' nodes do: the `blip_bs` mini-batches of
+    a step each contribute) and returns the token gradient - zero but for the CLS rows, which the kernel writes."""
+
+    @staticmethod
+    def forward(ctx, tokens, weight, bias):
+        t_hat, inv = T.pooled_head_fwd(tokens[:, 0], weight.detach(), bias.detach())
+        ctx.weight, ctx.bias = weight, bias
+        ctx.save_for_backward(tokens, t_hat, inv)
+        return t_hat
+
+    @staticmethod
+    def backward(ctx, dt_hat):
+        tokens, t_hat, inv = ctx.saved_tensors
+        weight, bias = ctx.weight, ctx.bias
+        sums = []
+        for p in (weight, bias):                                                    # the kernel adds into .grad where it can
+            ok = p.requires_grad and p.grad is not None and p.grad.dtype == torch.float32 and p.grad.is_contiguous() and p.grad.data_ptr() % 16 == 0
+            sums.append(p.grad if ok else torch.zeros(p.shape, dtype=torch.float32, device=tokens.device))
+        dtok = torch.zeros_like(tokens) if ctx.needs_input_grad[0] else None       # the rows the kernel does not write: zeroed here
+        T.pooled_head_bwd(dt_hat.contiguous().float(), t_hat, inv, tokens[:, 0], weight.detach(), sums[0], sums[1], None if dtok is None else dtok[:, 0])
+        for p, s in zip((weight, bias), sums):
+            if p.requires_grad and p.grad is not s:
+                p.grad = s if p.grad is None else T.eltwise(p.grad.contiguous().float(), T.MODE_ADD, s)
+        return dtok, None, None
+
+
+def pooled_head_train(tokens: torch.Tensor, weight: torch.nn.Parameter, bias: torch.nn.Parameter) -> torch.Tensor:
+    """(Bt, E) normalised pooled features of (Bt, N, Dv) fp32 tokens with a graph into vision_proj and into the tokens' CLS rows."""
+    if tokens.dtype != torch.float32 or not tokens.is_contiguous() or weight.dtype != torch.float32 or not weight.is_contiguous():
+        raise ValueError("pooled head (train mode): fp32 contiguous tokens and an fp32 vision_proj are required")
+    return _PooledHeadFn.apply(tokens, weight, bias)
 
 
 def _refuse_image_grads(*tensors):
@@ -225,8 +281,10 @@ def _refuse_image_grads(*tensors):
 
 
 def stage1_train(model, ref_tokens, target, ids, mask) -> torch.Tensor:
-    """(B, Bt) logits of `BLIP_Retrieval.img_txt_fusion(..., train=True)` in training mode, differentiable w.r.t. the 319 trained tensors."""
-    _refuse_image_grads(ref_tokens, target)
+    """(B, Bt) logits of `BLIP_Retrieval.img_txt_fusion(..., train=True)` in training mode, differentiable w.r.t. the 319 trained tensors -
+    and, on a model with `set_image_tuning()` on, w.r.t. `ref_tokens` and `target` where they require a gradient."""
+    if not getattr(model, "image_tuning", False):
+        _refuse_image_grads(ref_tokens, target)
     tr = getattr(model, "_trainer", None)
     g = model.bert_geometry
     if (not isinstance(tr, MedTrainer) or tr.dtype != train_dtype(model)

@@ -561,6 +561,29 @@ int cir_contrastive_fwd(const float* p, const float* target, const float* temp, 
 int cir_contrastive_bwd(const float* dlogits, const float* target, const float* temp, const float* p_hat, const float* inv_norm, float* dp,
                         float* row_scratch, float* dtemp, const float* x, int64_t ldx, const float* W, float* dx, int64_t lddx, float* dW, float* db,
                         int D, int B, int Bt, int E, int dtype, void* stream);
+/* Image side of the stage-I training step with a trained image encoder (stage1_train.py --blip-img-tune: :144-190 / :383-425; additive
+ * within ABI 15).  Same conventions as the pair above: fp32 only (CIR_EDTYPE otherwise), fixed-order reductions, no atomics - every output
+ * repeats bit for bit.
+ *   cir_contrastive_bwd_target (blip_stage1.py:91, the adjoint w.r.t. target_features - the transposed product cir_contrastive_bwd does not
+ *     form):  dtarget[j][:] = (1 / temp) sum_i dlogits[i][j] p_hat[i][:],  dlogits (B, Bt), p_hat (B, E), dtarget (Bt, E) WRITTEN, temp a
+ *     DEVICE pointer.  E % 4 == 0, E <= 1024, B, Bt <= 65535, B * Bt < 2^31.
+ *   cir_pooled_head_fwd (blip_stage1.py:57: F.normalize(vision_proj(image_embeds[:, 0, :]))):  t = x W^T + b,  t_hat = t / max(||t||, 1e-12).
+ *     x = Bt rows of D at stride ldx - the CLS rows of a (Bt, N, D) token tensor read in place with ldx = N * D -, W (E, D), b (E); writes
+ *     t_hat (Bt, E) and inv_norm (Bt) = 1 / max(||t||, 1e-12).  t_hat has the bits of cir_l2_normalize(cir_linear_f32(x, W, b)): the same
+ *     FMA chains in the same order.
+ *   cir_pooled_head_bwd, from dt_hat (Bt, E):  dt = inv_norm (dt_hat - t_hat (t_hat . dt_hat)) (a row the epsilon clamped: dt = dt_hat /
+ *     1e-12, as F.normalize differentiates) WRITTEN to dt (Bt, E, work space and result);  dW (E, D) += dt^T x and db (E) += column sums of
+ *     dt - both ADDED to what is there (the mini-batches of one step each contribute; rows in order, one adder per element);  dx = dt W
+ *     WRITTEN into Bt rows of D at stride lddx - the CLS rows of a (Bt, N, D) token-gradient tensor; the other rows are NOT touched: the
+ *     caller zeroes them.  dx may be NULL (frozen image encoder: vision_proj's gradients only).
+ * E % 4 == 0, E <= 1024, D % 4 == 0, D <= 2048, Bt <= 65535, ldx / lddx >= D and multiples of 4; 16-byte aligned matrices and rows, 4-byte
+ * aligned vectors (b, db, inv_norm). */
+int cir_contrastive_bwd_target(const float* dlogits, const float* p_hat, const float* temp, float* dtarget, int B, int Bt, int E, int dtype,
+                               void* stream);
+int cir_pooled_head_fwd(const float* x, int64_t ldx, const float* W, const float* bias, float* t_hat, float* inv_norm, int Bt, int E, int D,
+                        int dtype, void* stream);
+int cir_pooled_head_bwd(const float* dt_hat, const float* t_hat, const float* inv_norm, const float* x, int64_t ldx, const float* W, float* dt,
+                        float* dx, int64_t lddx, float* dW, float* db, int Bt, int E, int D, int dtype, void* stream);
 
 #ifdef __cplusplus
 }
