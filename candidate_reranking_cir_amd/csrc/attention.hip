@@ -606,14 +606,6 @@ static AttnArgs fill_attn_args(const HeadView& q, const HeadView& k, const HeadV
     return a;
 }
 
-// f(type tag, mask constant) for the 16-bit operand type and the presence of a mask
-template <typename T> struct TypeTag { using type = T; };
-template <typename F>
-static int by_dtype_mask(int dtype, bool masked, F&& f) {
-    if (dtype == CIR_BF16) return masked ? f(TypeTag<__bf16>{}, std::true_type{}) : f(TypeTag<__bf16>{}, std::false_type{});
-    return masked ? f(TypeTag<_Float16>{}, std::true_type{}) : f(TypeTag<_Float16>{}, std::false_type{});
-}
-
 }  // namespace cir
 
 extern "C" int cir_attention(const void* q, int64_t q_s1, int64_t q_s0, int64_t q_rs, const void* k, int64_t k_s1,

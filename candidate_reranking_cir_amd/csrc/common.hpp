@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "cirrank.h"
 
@@ -85,6 +86,11 @@ __device__ __forceinline__ float fast_erf(float x) {
     return copysignf(e, x);
 }
 __device__ __forceinline__ float gelu_erf_as(float x) { return 0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752f)); }   // (scalar form of gelu_erf_as8: tools / reference for it)
+
+// d/dx of the exact erf-GELU (the training pass: cir_eltwise mode 1 in train.hip, cir_rows16_colsum mode 1 in train_fused.hip)
+__device__ __forceinline__ float gelu_grad(float x) {
+    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
+}
 
 // erf-GELU x * Phi(x) through a logistic fit of the normal CDF, Phi(x) ~ 1 / (1 + 2^-q(x)), q an odd degree-7
 // polynomial (minimax fit of x*Phi(x) on [-7, 7], max |error| 1.2e-5 in fp32 - an order of magnitude under the
@@ -302,3 +308,18 @@ int colsum_ordered_launch(const float* x, int64_t ld, int64_t rows, int seg, con
 #define CIR_CHECK_PTR(p) do { if ((p) == nullptr) return CIR_EINVAL; } while (0)
 #define CIR_LAUNCH_RESULT() do { hipError_t e_ = hipGetLastError(); return e_ == hipSuccess ? CIR_OK : (int)e_; } while (0)
 static inline bool cir_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---- operand-type dispatch: ONE launch line per entry point, written as a generic lambda over type tags and compile-time flags ----------
+//   by_dtype16(dtype, [&](auto t) { using T = typename decltype(t)::type; hipLaunchKernelGGL((kernel<T>), ...); });
+// The caller has validated `dtype` (the helpers return what f returns and no codes of their own): anything that is not CIR_BF16 goes to
+// _Float16, in by_dtype3 anything that is neither CIR_F32 nor CIR_BF16.
+namespace cir {
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> static inline auto by_dtype16(int dtype, F&& f) { return dtype == CIR_BF16 ? f(TypeTag<__bf16>{}) : f(TypeTag<_Float16>{}); }
+template <typename F> static inline auto by_dtype3(int dtype, F&& f) { return dtype == CIR_F32 ? f(TypeTag<float>{}) : by_dtype16(dtype, f); }
+template <typename F> static inline auto by_bool(bool flag, F&& f) { return flag ? f(std::true_type{}) : f(std::false_type{}); }
+// f(type tag, mask constant) for the 16-bit operand type and the presence of a mask
+template <typename F> static inline auto by_dtype_mask(int dtype, bool masked, F&& f) {
+    return by_dtype16(dtype, [&](auto t) { return by_bool(masked, [&](auto mk) { return f(t, mk); }); });
+}
+}  // namespace cir

@@ -421,9 +421,9 @@ extern "C" int cir_attention_train_fwd(const void* q, int64_t q_sg, int64_t q_sh
     const int64_t units = (int64_t)G * H * a.nqt;
     dim3 grid((unsigned)((units + 3) / 4)), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool mk = mask != nullptr;
-    if (dtype == CIR_BF16) { if (mk) hipLaunchKernelGGL((tattn_fwd_kernel<__bf16, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((tattn_fwd_kernel<__bf16, false>), grid, block, 0, s, a); }
-    else { if (mk) hipLaunchKernelGGL((tattn_fwd_kernel<_Float16, true>), grid, block, 0, s, a); else hipLaunchKernelGGL((tattn_fwd_kernel<_Float16, false>), grid, block, 0, s, a); }
+    by_dtype_mask(dtype, mask != nullptr, [&](auto t, auto mk) {
+        hipLaunchKernelGGL((tattn_fwd_kernel<typename decltype(t)::type, decltype(mk)::value>), grid, block, 0, s, a);
+    });
     CIR_LAUNCH_RESULT();
 }
 
@@ -458,17 +458,13 @@ extern "C" int cir_attention_train_bwd(const void* q, int64_t q_sg, int64_t q_sh
     for (int64_t st : s32)
         if (st % 4) return CIR_EALIGN;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool mk = mask != nullptr;
     dim3 block(256);
     dim3 gq((unsigned)(((int64_t)G * H * a.nqt + 3) / 4)), gk((unsigned)(((int64_t)G * H * a.nkt + 3) / 4));
     // dQ first: it also writes D = rowsum(dO * O), which the dK / dV kernel reads (same stream: ordered)
-    const bool dr = p_drop > 0.f;
-#define CIR_TATTN_BWD(TT, MK, DR) do { hipLaunchKernelGGL((tattn_bwd_dq_kernel<TT, MK, DR>), gq, block, 0, s, a); \
-                                       hipLaunchKernelGGL((tattn_bwd_dkv_kernel<TT, MK, DR>), gk, block, 0, s, a); } while (0)
-#define CIR_TATTN_BWD_T(TT) do { if (mk) { if (dr) CIR_TATTN_BWD(TT, true, true); else CIR_TATTN_BWD(TT, true, false); } \
-                                 else { if (dr) CIR_TATTN_BWD(TT, false, true); else CIR_TATTN_BWD(TT, false, false); } } while (0)
-    if (dtype == CIR_BF16) CIR_TATTN_BWD_T(__bf16); else CIR_TATTN_BWD_T(_Float16);
-#undef CIR_TATTN_BWD_T
-#undef CIR_TATTN_BWD
+    by_dtype_mask(dtype, mask != nullptr, [&](auto t, auto mk) { by_bool(p_drop > 0.f, [&](auto dr) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((tattn_bwd_dq_kernel<T, decltype(mk)::value, decltype(dr)::value>), gq, block, 0, s, a);
+        hipLaunchKernelGGL((tattn_bwd_dkv_kernel<T, decltype(mk)::value, decltype(dr)::value>), gk, block, 0, s, a);
+    }); });
     CIR_LAUNCH_RESULT();
 }

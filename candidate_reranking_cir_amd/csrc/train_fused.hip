@@ -197,10 +197,6 @@ __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const float* x, const
 // ---- 16-bit rows: column sums, optionally behind dz = a * gelu'(z) -----------------------------------------------------------------
 // block = 32 column groups (8 columns each: one 16-byte load) x 8 row lanes, 64 rows per block; column sums over the block's rows in
 // registers, then across the row lanes through LDS, one atomic per column and block.
-__device__ __forceinline__ float gelu_grad_f(float x) {
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-
 // ORD (deterministic mode, cir_rows16_colsum_ordered): `sums` is the partial workspace, the block stores to its row blockIdx.y.
 template <typename T, int MODE, bool ORD>      // MODE 0: sums of a;  1: out = a * gelu'(z), sums of out
 __global__ __launch_bounds__(256) void rows16_colsum_kernel(const T* a, int64_t lda, const T* z, int64_t ldz, T* out, int64_t ldo, float* sums,
@@ -223,7 +219,7 @@ __global__ __launch_bounds__(256) void rows16_colsum_kernel(const T* a, int64_t 
                 X8 o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float v = static_cast<float>(av[e]) * gelu_grad_f(static_cast<float>(zv[e]));
+                    const float v = static_cast<float>(av[e]) * gelu_grad(static_cast<float>(zv[e]));
                     o[e] = static_cast<T>(v);
                     acc[e] += v;
                 }
@@ -280,10 +276,11 @@ extern "C" int cir_rows_scale_add(const float* a, const float* b, const float* s
     const int64_t n4 = rows * cols / 4;
     dim3 grid((unsigned)((n4 + 255) / 256)), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (out_dtype == CIR_F32) hipLaunchKernelGGL((rows_scale_add_kernel<float>), grid, block, 0, s, a, b, scale, reinterpret_cast<float*>(out), rows, cols, rows_per_group);
-    else if (out_dtype == CIR_BF16) hipLaunchKernelGGL((rows_scale_add_kernel<__bf16>), grid, block, 0, s, a, b, scale, reinterpret_cast<__bf16*>(out), rows, cols, rows_per_group);
-    else if (out_dtype == CIR_F16) hipLaunchKernelGGL((rows_scale_add_kernel<_Float16>), grid, block, 0, s, a, b, scale, reinterpret_cast<_Float16*>(out), rows, cols, rows_per_group);
-    else return CIR_EDTYPE;
+    if (out_dtype != CIR_F32 && out_dtype != CIR_BF16 && out_dtype != CIR_F16) return CIR_EDTYPE;
+    by_dtype3(out_dtype, [&](auto t) {
+        using TO = typename decltype(t)::type;
+        hipLaunchKernelGGL((rows_scale_add_kernel<TO>), grid, block, 0, s, a, b, scale, reinterpret_cast<TO*>(out), rows, cols, rows_per_group);
+    });
     CIR_LAUNCH_RESULT();
 }
 
@@ -298,12 +295,11 @@ extern "C" int cir_residual_layernorm_train(const float* t0, const float* t1, co
         !cir_aligned16(beta) || (reinterpret_cast<uintptr_t>(y16) & 7u)) return CIR_EALIGN;
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype16 == CIR_BF16)
-        hipLaunchKernelGGL((res_ln_train_kernel<__bf16>), grid, block, 0, s, t0, t1, residual, gamma, beta, pre, y32, reinterpret_cast<__bf16*>(y16), rows,
-                           cols, eps, alpha, p_drop, seed);
-    else
-        hipLaunchKernelGGL((res_ln_train_kernel<_Float16>), grid, block, 0, s, t0, t1, residual, gamma, beta, pre, y32, reinterpret_cast<_Float16*>(y16),
-                           rows, cols, eps, alpha, p_drop, seed);
+    by_dtype16(dtype16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((res_ln_train_kernel<T>), grid, block, 0, s, t0, t1, residual, gamma, beta, pre, y32, reinterpret_cast<T*>(y16), rows, cols,
+                           eps, alpha, p_drop, seed);
+    });
     CIR_LAUNCH_RESULT();
 }
 
@@ -329,10 +325,11 @@ extern "C" int cir_layernorm_bwd_fused(const float* x, const float* gamma, const
     // the column-sum atomics (3 x 768 per block) outweigh the occupancy gained
     dim3 block(256), grid((unsigned)((rows + 31) / 32));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define CIR_LNB(TT) hipLaunchKernelGGL((ln_bwd_fused_kernel<TT, 8, false>), grid, block, 0, s, x, gamma, dy, dx, dgamma, dbeta, t_add, \
-                                       reinterpret_cast<TT*>(dt16), dbias, dbias2, rows, cols, eps, alpha, p_drop, seed, (float*)nullptr)
-    if (dtype16 == CIR_BF16) CIR_LNB(__bf16); else CIR_LNB(_Float16);
-#undef CIR_LNB
+    by_dtype16(dtype16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((ln_bwd_fused_kernel<T, 8, false>), grid, block, 0, s, x, gamma, dy, dx, dgamma, dbeta, t_add, reinterpret_cast<T*>(dt16),
+                           dbias, dbias2, rows, cols, eps, alpha, p_drop, seed, (float*)nullptr);
+    });
     CIR_LAUNCH_RESULT();
 }
 
@@ -348,10 +345,11 @@ extern "C" int cir_layernorm_bwd_fused_ordered(const float* x, const float* gamm
     if (partial_elems < blocks * (bias ? 3 : 2) * cols) return CIR_ESHAPE;
     dim3 block(256), grid((unsigned)blocks);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define CIR_LNB(TT) hipLaunchKernelGGL((ln_bwd_fused_kernel<TT, 8, true>), grid, block, 0, s, x, gamma, dy, dx, dgamma, dbeta, t_add, \
-                                       reinterpret_cast<TT*>(dt16), dbias, dbias2, rows, cols, eps, alpha, p_drop, seed, partials)
-    if (dtype16 == CIR_BF16) CIR_LNB(__bf16); else CIR_LNB(_Float16);
-#undef CIR_LNB
+    by_dtype16(dtype16, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((ln_bwd_fused_kernel<T, 8, true>), grid, block, 0, s, x, gamma, dy, dx, dgamma, dbeta, t_add, reinterpret_cast<T*>(dt16),
+                           dbias, dbias2, rows, cols, eps, alpha, p_drop, seed, partials);
+    });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     OrderedDst d{};
@@ -378,13 +376,11 @@ static int rows16_colsum(const void* a, int64_t lda, const void* z, int64_t ldz,
     if (ord && partial_elems < row_blocks * cols) return CIR_ESHAPE;
     dim3 grid((cols + 255) / 256, (unsigned)row_blocks), block(256);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define CIR_R16(T, MODE, ORD, SUMS) hipLaunchKernelGGL((rows16_colsum_kernel<T, MODE, ORD>), grid, block, 0, s, reinterpret_cast<const T*>(a), lda, \
-                                                       reinterpret_cast<const T*>(z), ldz, reinterpret_cast<T*>(out), ldo, SUMS, rows, cols)
-#define CIR_R16_T(T) do { if (ord) { if (mode) CIR_R16(T, 1, true, partials); else CIR_R16(T, 0, true, partials); } \
-                          else { if (mode) CIR_R16(T, 1, false, sums); else CIR_R16(T, 0, false, sums); } } while (0)
-    if (dtype == CIR_BF16) CIR_R16_T(__bf16); else CIR_R16_T(_Float16);
-#undef CIR_R16_T
-#undef CIR_R16
+    by_dtype16(dtype, [&](auto t) { by_bool(mode != 0, [&](auto md) { by_bool(ord, [&](auto od) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((rows16_colsum_kernel<T, decltype(md)::value ? 1 : 0, decltype(od)::value>), grid, block, 0, s, reinterpret_cast<const T*>(a), lda,
+                           reinterpret_cast<const T*>(z), ldz, reinterpret_cast<T*>(out), ldo, ord ? partials : sums, rows, cols);
+    }); }); });
     if (!ord) CIR_LAUNCH_RESULT();
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;

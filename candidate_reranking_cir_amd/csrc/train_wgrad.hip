@@ -227,8 +227,7 @@ extern "C" int cir_wgrad_grouped(const cir_wgrad_desc* d, int count, int in_dtyp
             if (units > 0x7fffffff) return CIR_ESHAPE;
         }
         a.count = n_act; a.units = (int)units;
-        if (in_dtype == CIR_BF16) hipLaunchKernelGGL((wgrad_kernel<__bf16>), dim3((unsigned)units), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((wgrad_kernel<_Float16>), dim3((unsigned)units), dim3(256), 0, s, a);
+        by_dtype16(in_dtype, [&](auto t) { hipLaunchKernelGGL((wgrad_kernel<typename decltype(t)::type>), dim3((unsigned)units), dim3(256), 0, s, a); });
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }

@@ -388,9 +388,10 @@ extern "C" int cir_cross_attention_folded(const void* q, int64_t q_sb, int64_t q
     if (rc != CIR_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (N > 16 * kFoldKB) return launch_fold16(a, dtype, s);       // 225 .. 608 keys: the 16-rows-per-wave kernel (xattn_fold_units.hip)
-    const FoldKernel k = dtype == CIR_BF16 ? (key_mask ? xattn_fold_kernel<__bf16, true> : xattn_fold_kernel<__bf16, false>)
-                                           : (key_mask ? xattn_fold_kernel<_Float16, true> : xattn_fold_kernel<_Float16, false>);
-    return fold_launch(k, dim3((unsigned)(8 * ((T + 3) / 4))), dim3(512), 2 * kFoldBuf + 32 * kStrideQ, s, a);
+    return by_dtype_mask(dtype, key_mask != nullptr, [&](auto t, auto mk) {
+        const FoldKernel k = &xattn_fold_kernel<typename decltype(t)::type, decltype(mk)::value>;
+        return fold_launch(k, dim3((unsigned)(8 * ((T + 3) / 4))), dim3(512), 2 * kFoldBuf + 32 * kStrideQ, s, a);
+    });
 }
 
 #if FOLD_DBG & 8

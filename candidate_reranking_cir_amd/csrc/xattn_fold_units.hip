@@ -407,9 +407,10 @@ static int launch_fold_units(FoldKernel kernel, const FoldArgs& a, hipStream_t s
 }
 
 int launch_fold16(const FoldArgs& a, int dtype, hipStream_t s) {
-    const FoldKernel k = dtype == CIR_BF16 ? (a.mask ? xattn_fold16_kernel<__bf16, true> : xattn_fold16_kernel<__bf16, false>)
-                                           : (a.mask ? xattn_fold16_kernel<_Float16, true> : xattn_fold16_kernel<_Float16, false>);
-    return launch_fold_units<1, 2, 38>(k, a, s);
+    return by_dtype_mask(dtype, a.mask != nullptr, [&](auto t, auto mk) {
+        const FoldKernel k = &xattn_fold16_kernel<typename decltype(t)::type, decltype(mk)::value>;
+        return launch_fold_units<1, 2, 38>(k, a, s);
+    });
 }
 
 // cost in 16-row steps: 1, 2 or 3 blocks per wave and head up to 48 tokens, two waves of 2 blocks per head above
@@ -447,8 +448,7 @@ extern "C" int cir_cross_attention_folded_long(const void* q, int64_t q_sb, int6
                              64, 16 * kFoldKB, (int64_t)T * 6 + 8);
     if (rc != CIR_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == CIR_BF16) return key_mask ? launch_fold_long<__bf16, true>(a, s) : launch_fold_long<__bf16, false>(a, s);
-    return key_mask ? launch_fold_long<_Float16, true>(a, s) : launch_fold_long<_Float16, false>(a, s);
+    return by_dtype_mask(dtype, key_mask != nullptr, [&](auto t, auto mk) { return launch_fold_long<typename decltype(t)::type, decltype(mk)::value>(a, s); });
 }
 
 // The query-side fold for captions of at most 16 tokens (nlvr_encoder.py:150-168, 183-217; blip_stage2.py:113: batch 1, padding='longest' -
@@ -462,8 +462,7 @@ extern "C" int cir_cross_attention_folded_short(const void* q, int64_t q_sb, int
                              16, 608, (int64_t)T * 6 + 8);
     if (rc != CIR_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == CIR_BF16) return key_mask ? launch_fold_short<__bf16, true>(a, s) : launch_fold_short<__bf16, false>(a, s);
-    return key_mask ? launch_fold_short<_Float16, true>(a, s) : launch_fold_short<_Float16, false>(a, s);
+    return by_dtype_mask(dtype, key_mask != nullptr, [&](auto t, auto mk) { return launch_fold_short<typename decltype(t)::type, decltype(mk)::value>(a, s); });
 }
 
 // The query-side fold for captions of 33 .. 64 tokens (nlvr_encoder.py:150-168, 183-217; blip_stage2.py:113: padding='longest', no 32-token
@@ -478,6 +477,5 @@ extern "C" int cir_cross_attention_folded_long_wide(const void* q, int64_t q_sb,
                              64, 608, (int64_t)T * 12 + 8, 33, 225);
     if (rc != CIR_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == CIR_BF16) return key_mask ? launch_fold_wide<__bf16, true>(a, s) : launch_fold_wide<__bf16, false>(a, s);
-    return key_mask ? launch_fold_wide<_Float16, true>(a, s) : launch_fold_wide<_Float16, false>(a, s);
+    return by_dtype_mask(dtype, key_mask != nullptr, [&](auto t, auto mk) { return launch_fold_wide<typename decltype(t)::type, decltype(mk)::value>(a, s); });
 }
