@@ -103,10 +103,22 @@ class BLIP_Retrieval(_EngineHost):
             out += (torch.ones(y32.shape[:-1], dtype=torch.long, device=y32.device),)
         return out[0] if len(out) == 1 else out
 
+    def img_embed_raw(self, images, transform, atts=False, return_pool_and_normalized=False):
+        """`img_embed` from decoded uint8 RGB images of any sizes and a `preprocess.DeviceTransform` (data_utils.py:71-101 on the device).
+        Without a graph the transform writes the ViT's patch operand rows directly (no fp32 image tensor, no patchify launch); the results
+        are those of `img_embed(transform.batch(images))` bit for bit.  With `set_image_tuning()` building a graph, the normalised
+        (B,3,H,W) tensor goes to `img_embed`."""
+        if any(self._image_side_trained(return_pool_and_normalized)):
+            return self.img_embed(transform.batch(images, dtype=torch.float32), atts, return_pool_and_normalized)
+        return self._img_embed_frozen(None, atts, return_pool_and_normalized, patches=transform.batch(images, patches=True, dtype=self.token_dtype))
+
     @torch.no_grad()
-    def _img_embed_frozen(self, image, atts=False, return_pool_and_normalized=False):
+    def _img_embed_frozen(self, image, atts=False, return_pool_and_normalized=False, patches=None):
         _, vit, heads = self.engines()
-        y32, _ = vit.forward(image.to(self.device), want32=True)
+        if patches is not None:
+            y32, _ = vit.forward(None, want32=True, patches=patches)
+        else:
+            y32, _ = vit.forward(image.to(self.device), want32=True)
         out = (y32,)
         if return_pool_and_normalized:
             out += (ops.l2_normalize(ops.linear_f32(y32[:, 0, :], heads["vw"], heads["vb"])),)

@@ -397,6 +397,20 @@ class BLIP_NLVR(_EngineHost):
         """Same tokens in the 16-bit `token_dtype` (what the cross-attention K|V GEMMs consume)."""
         return self.engines(text=False)[0].forward(image.to(self.device), want32=False)[1]
 
+    def img_embed_raw(self, images, transform, train=True, atts=False):
+        """`img_embed` from decoded uint8 RGB images of any sizes (arrays / tensors / PIL images) and a `preprocess.DeviceTransform`
+        (the reference's `preprocess`, data_utils.py:71-101, on the device).  Eval mode: the transform writes the ViT's patch operand
+        rows directly - no fp32 image tensor, no patchify launch - and the tokens are those of `img_embed(transform.batch(images))` bit
+        for bit.  In `.train()` mode (a ViT with a graph, or DropPath draws) the normalised (B,3,H,W) tensor goes to `img_embed`."""
+        if self.training:
+            return self.img_embed(transform.batch(images, dtype=torch.float32), train=train, atts=atts)
+        with torch.no_grad():
+            rows = transform.batch(images, patches=True, dtype=self.token_dtype)
+            y32, _ = self.engines(text=False)[0].forward(None, want32=True, patches=rows)
+        if atts:
+            return y32, torch.ones(y32.shape[:-1], dtype=torch.long, device=y32.device)
+        return y32
+
     def _cand16(self, t_image_embeds: torch.Tensor) -> torch.Tensor:
         t = t_image_embeds.to(self.device)
         if t.dtype == self.token_dtype:

@@ -141,11 +141,15 @@ class VitEngine:
                 if self.ln_fold >= 2:     # norm2 -> fc1 only on request (measured slower: 57 MB of packed weights nobody reads otherwise)
                     blk["fc1_f"] = ops.ln_fold_pack(sd[b + "mlp.fc1.weight"].to(device), sd[b + "mlp.fc1.bias"].to(device), blk["g2"], blk["b2"])
 
-    def forward(self, image: torch.Tensor, want32: bool = False, chunk: int = 4096, out32: Optional[torch.Tensor] = None,
-                out16: Optional[torch.Tensor] = None):
+    def forward(self, image: Optional[torch.Tensor], want32: bool = False, chunk: int = 4096, out32: Optional[torch.Tensor] = None,
+                out16: Optional[torch.Tensor] = None, patches: Optional[torch.Tensor] = None):
         """(B,3,H,W) fp32/16-bit -> tokens (B, N, D): 16-bit always, fp32 too if `want32`.  `out32` / `out16`: write the
         tokens there (contiguous (B, N, D) tensors) - the chunked path hands each chunk its slice of ONE result tensor, so
-        no concatenation copy follows (2 GB per 6784 images at 224 px)."""
+        no concatenation copy follows (2 GB per 6784 images at 224 px).  `patches` (default None): the patch operand rows
+        (B * P, 3 p p) in the engine's operand type, as ops.patchify writes them - the device transform's direct output
+        (preprocess.DeviceTransform.batch(..., patches=True)); `image` is then ignored and no patchify launch is issued."""
+        if patches is not None:
+            return self._forward_patches(patches, want32, chunk, out32, out16)
         geo, dt = self.geo, self.dtype
         bsz, d, n = image.shape[0], geo.width, geo.num_tokens
         if bsz > chunk:
@@ -163,9 +167,34 @@ class VitEngine:
             raise ValueError(f"image size {tuple(image.shape[-2:])} != model image_size {geo.image_size}")
         if image.dtype not in (torch.float32, dt):
             image = image.float()
+        return self._encode(ops.patchify(image, geo.patch_size, dt), bsz, want32, out32, out16)   # PatchEmbed im2col
+
+    def _forward_patches(self, patches: torch.Tensor, want32: bool, chunk: int, out32: Optional[torch.Tensor], out16: Optional[torch.Tensor]):
+        """`forward` from the patch operand rows: the same chunking, no patchify launch."""
+        geo, dt = self.geo, self.dtype
+        p, d, n = geo.num_tokens - 1, geo.width, geo.num_tokens
+        if patches.dim() != 2 or patches.dtype != dt or patches.shape[1] != 3 * geo.patch_size ** 2 or patches.shape[0] % p or not patches.is_contiguous():
+            raise ValueError(f"patch rows {tuple(patches.shape)} {patches.dtype}: expected contiguous (B * {p}, {3 * geo.patch_size ** 2}) {dt}")
+        bsz = patches.shape[0] // p
+        if bsz <= chunk:
+            return self._encode(patches, bsz, want32, out32, out16)
+        n_parts = -(-bsz // chunk)
+        size = -(-bsz // n_parts)
+        y16 = torch.empty((bsz, n, d), dtype=dt, device=patches.device) if out16 is None else out16
+        if dt == torch.float32 and want32 and out32 is None:
+            y32 = y16
+        else:
+            y32 = (torch.empty((bsz, n, d), dtype=torch.float32, device=patches.device) if out32 is None else out32) if want32 else None
+        for i in range(0, bsz, size):
+            self._encode(patches[i * p:(i + size) * p], min(size, bsz - i), want32, None if y32 is None else y32[i:i + size], y16[i:i + size])
+        return y32, y16
+
+    def _encode(self, patches: torch.Tensor, bsz: int, want32: bool, out32: Optional[torch.Tensor], out16: Optional[torch.Tensor]):
+        """Patch rows (bsz * P, 3 p p) -> tokens: everything of `forward` behind the im2col."""
+        geo, dt = self.geo, self.dtype
+        d, n = geo.width, geo.num_tokens
         scale = 64 ** -0.5                                                     # vit.py:50
         sdt = self.stream_dtype
-        patches = ops.patchify(image, geo.patch_size, dt)                      # PatchEmbed im2col
         proj = ops.gemm(patches, self.w_patch, self.b_patch, out_dtype=sdt)
         x = ops.vit_assemble(proj, self.cls, self.pos, bsz).view(bsz * n, d)   # vit.py:184-187 (residual stream, sdt)
         ctx = torch.empty((bsz, n, d), dtype=dt, device=x.device)

@@ -564,6 +564,18 @@ def patchify(image: torch.Tensor, patch: int, dtype16: torch.dtype = torch.bfloa
     return out
 
 
+def preprocess_images(src: torch.Tensor, src_bytes: int, desc: torch.Tensor, taps: torch.Tensor, taps_len: int, table: Optional[torch.Tensor],
+                      out: torch.Tensor, batch: int, dim: int, layout: int) -> torch.Tensor:
+    """cir_preprocess_images on device views of one packed buffer (preprocess.DeviceTransform.pack lays it out): `src` uint8 pixels,
+    `desc` / `taps` the int32 tables as bytes, `table` the 768 values in out's type (None for the raw uint8 layout); writes `out`."""
+    _need_cuda(src, desc, taps, table, out)
+    assert out.is_contiguous() and (table is None or (table.dtype == out.dtype and table.numel() == 768))
+    code = _lib.load().cir_preprocess_images(src.data_ptr(), src_bytes, desc.data_ptr(), taps.data_ptr(), taps_len, _ptr(table), out.data_ptr(),
+                                             batch, dim, layout, _DT.get(out.dtype, CIR_F32), _stream())
+    _lib.check(code, "cir_preprocess_images")
+    return out
+
+
 def vit_assemble(proj: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, batch: int) -> torch.Tensor:
     """proj (B*P, D) in the stream dtype (fp32 / fp16), cls (D), pos (P+1, D) fp32 -> x (B, P+1, D) in proj.dtype."""
     _need_cuda(proj, cls, pos)

@@ -34,6 +34,18 @@ def extract_index_features(images: torch.Tensor, model_stage1, batch_size: int =
 
 
 @torch.no_grad()
+def extract_index_features_raw(images: Sequence, model_stage1, transform, batch_size: int = 64):
+    """`extract_index_features` from decoded uint8 RGB images of any sizes and a `preprocess.DeviceTransform` (data_utils.py:71-101 on the
+    device, patch operand rows out: no fp32 image tensor exists).  Same results, bit for bit, as on `transform.batch(images)`."""
+    toks, pooled = [], []
+    for i in range(0, len(images), batch_size):
+        t32, p = model_stage1.img_embed_raw(images[i:i + batch_size], transform, return_pool_and_normalized=True)
+        toks.append(ops.gather_rows(t32, None, model_stage1.token_dtype))
+        pooled.append(p)
+    return torch.cat(toks), torch.cat(pooled)
+
+
+@torch.no_grad()
 def generate_val_predictions(model_stage1, ref_index: np.ndarray, captions: Sequence[str], index_tokens: torch.Tensor,
                              batch_size: int = 32) -> torch.Tensor:
     """validate.py:100-147 / 281-330: fused, normalised query features (Q, 256); captions are padded per batch of 32

@@ -65,6 +65,22 @@ def extract_index_features(images: torch.Tensor, model, batch_size: int = 64, dt
     return torch.cat(outs)
 
 
+@torch.no_grad()
+def extract_index_features_raw(images: Sequence, model, transform, batch_size: int = 64, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """`extract_index_features` from decoded uint8 RGB images of any sizes (arrays / tensors / PIL images) and a
+    `preprocess.DeviceTransform`: per batch the transform (data_utils.py:71-101) writes the ViT's patch operand rows directly, so no fp32
+    image tensor ever exists.  Same bank, bit for bit, as `extract_index_features(transform.batch(images), model)`."""
+    outs = []
+    for i in range(0, len(images), batch_size):
+        chunk = images[i:i + batch_size]
+        if dtype == torch.float32:
+            outs.append(model.img_embed_raw(chunk, transform))
+        else:                                                            # (`img_embed16` from the patch rows)
+            rows = transform.batch(chunk, patches=True, dtype=model.token_dtype)
+            outs.append(model.engines(text=False)[0].forward(None, want32=False, patches=rows)[1])
+    return torch.cat(outs)
+
+
 def _tokenise(ds: RelativeValSet, tokenizer, rows: Sequence[int], length: int, device):
     if ds.input_ids is not None:
         sel = list(rows)

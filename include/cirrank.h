@@ -300,6 +300,34 @@ int cir_patchify(const void* image, int img_dtype, void* patches, int dtype16,
                  int B, int C, int H, int Wd, int patch, void* stream);
 
 /*
+ * The reference's image transform (data_utils.py:23-101: TargetPad | SquarePad -> Resize(dim, BICUBIC) -> CenterCrop(dim) -> ToTensor ->
+ * Normalize) from decoded uint8 RGB images of any sizes, one launch per batch (csrc/preprocess.hip; additive within ABI v15).  Bit for bit
+ * PIL's 8-bit resize: two separable integer passes (horizontal first) over a uint8 intermediate,
+ *     pixel = clip8(((1 << 21) + sum_j kk[j] * p[xmin + j]) >> 22),   int32 throughout, arithmetic shift
+ * with the 22-bit fixed-point coefficients of libImaging's precompute_coeffs handed in as tables (the host forms them in float64:
+ * candidate_reranking_cir_amd/preprocess.py: resample_taps).  The zero pad is never materialised: a coordinate of the padded image outside
+ * the source reads 0.  Only the dim x dim pixels that survive the centre crop are computed.
+ *   src        B images packed in one uint8 buffer of src_bytes bytes, each (h, w, 3) HWC RGB, each starting 16-byte aligned
+ *   desc       B descriptors of 16 int32: {offset / 16, h, w, hp, vp, padded w, padded h, crop left, crop top, horizontal tap table
+ *              (offset into taps, row stride), vertical tap table (offset, row stride), resized w, resized h, 0}
+ *   taps       taps_len int32.  A tap table has one row per SURVIVING output coordinate (dim rows): {xmin, count, kk[0 .. count)} in
+ *              coordinates of the padded image, rows `row stride` (>= 2 + the largest count) int32 apart.  A pass PIL skips (extent
+ *              unchanged) is the table {x, 1, 1 << 22}, which reproduces the pixel exactly.
+ *   table      768 values in the output type: table[c * 256 + u] = ((u / 255) - mean_c) / std_c as torch forms it in fp32 (ToTensor +
+ *              Normalize, data_utils.py:82-83 / 99-100), converted to the output type by the host; unused (may be NULL) for CIR_PRE_RAW
+ *   out        layout CIR_PRE_CHW: (B, 3, dim, dim) in dtype;  CIR_PRE_PATCHES: cir_patchify's operand rows (B (dim / 16)^2, 3 * 16 * 16),
+ *              column order (c, ky, kx), in dtype (dim % 16 == 0, CIR_ESHAPE otherwise);  CIR_PRE_RAW: (B, dim, dim, 3) uint8, the resized
+ *              and cropped image itself (dtype ignored)
+ * dtype CIR_F32 / CIR_F16 / CIR_BF16.  Every source read is checked against the image's extent and the buffer's size, every tap-table row
+ * against taps_len, every tap count against its row stride: no content of desc / taps can cause an access outside the buffers (a
+ * descriptor that does not fit its buffer yields the image of an all-zero source).  Coefficients are multiplied as signed 24-bit values
+ * (PIL's stay below 1.3 * 2^22 in magnitude).  dim <= 4096; src, desc, taps, table, out 16-byte aligned.
+ */
+enum { CIR_PRE_CHW = 0, CIR_PRE_PATCHES = 1, CIR_PRE_RAW = 2 };
+int cir_preprocess_images(const uint8_t* src, int64_t src_bytes, const int32_t* desc, const int32_t* taps, int64_t taps_len, const void* table,
+                          void* out, int B, int dim, int layout, int dtype, void* stream);
+
+/*
  * Token assembly (vit.py:184-187): x[b][0] = cls + pos[0]; x[b][1+i] = proj[b*P+i] + pos[1+i].
  *   proj (B*P, D) (patch-embed GEMM output incl. bias) and x in stream_dtype (CIR_F32 / CIR_F16),
  *   cls (D), pos (P+1, D) fp32 parameters.  D % 8 == 0.
