@@ -220,12 +220,14 @@ def attention_train_bwd(q4, k4, v4, mask, out4, dout4, lse, dq4, dk4, dv4, scale
 
 
 def layernorm_bwd(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, dgamma: torch.Tensor, dbeta: torch.Tensor, eps: float,
-                  work: Optional[Workspace] = None) -> torch.Tensor:
-    """x, dy fp32 (rows, cols) contiguous; dgamma / dbeta fp32 (cols) are ACCUMULATED into -> dx fp32.  `work`: cir_layernorm_bwd_ordered."""
-    _need_cuda(x, gamma, dy, dgamma, dbeta)
+                  work: Optional[Workspace] = None, dx: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x, dy fp32 (rows, cols) contiguous; dgamma / dbeta fp32 (cols) are ACCUMULATED into -> dx fp32 (may be given: a contiguous row
+    range of a larger buffer).  `work`: cir_layernorm_bwd_ordered."""
+    _need_cuda(x, gamma, dy, dgamma, dbeta, dx)
     rows, cols = x.shape
     assert x.dtype == dy.dtype == gamma.dtype == dgamma.dtype == dbeta.dtype == torch.float32 and x.is_contiguous() and dy.is_contiguous()
-    dx = torch.empty_like(x)
+    dx = torch.empty_like(x) if dx is None else dx
+    assert dx.dtype == torch.float32 and dx.shape == x.shape and dx.is_contiguous()
     if work is not None:
         part = work.f32((rows + 31) // 32 * 2 * cols, x.device)
         _lib.check(_lib.load().cir_layernorm_bwd_ordered(x.data_ptr(), gamma.data_ptr(), dy.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
@@ -306,13 +308,15 @@ def colsum16(a: torch.Tensor, sums: torch.Tensor, work: Optional[Workspace] = No
     return sums
 
 
-def gelu_bwd16(df: torch.Tensor, z: torch.Tensor, sums: Optional[torch.Tensor] = None, work: Optional[Workspace] = None) -> torch.Tensor:
+def gelu_bwd16(df: torch.Tensor, z: torch.Tensor, sums: Optional[torch.Tensor] = None, work: Optional[Workspace] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dz = df * gelu'(z) on 16-bit (rows, cols) tensors; sums (cols) fp32 += column sums of dz (the dense layer's bias gradient; `work`: in
-    the fixed order of cir_rows16_colsum_ordered)."""
-    _need_cuda(df, z, sums)
+    the fixed order of cir_rows16_colsum_ordered).  `out` may be given (unit last stride, row stride a multiple of 8)."""
+    _need_cuda(df, z, sums, out)
     assert df.dim() == 2 and df.shape == z.shape and df.dtype == z.dtype and df.stride(1) == 1 and z.stride(1) == 1
     assert sums is None or (sums.dtype == torch.float32 and sums.shape == (df.shape[1],) and sums.is_contiguous())
-    out = torch.empty(df.shape, dtype=df.dtype, device=df.device)
+    out = torch.empty(df.shape, dtype=df.dtype, device=df.device) if out is None else out
+    assert out.shape == df.shape and out.dtype == df.dtype and out.stride(1) == 1 and out.stride(0) % 8 == 0
     if work is not None and sums is not None:
         _rows16_ordered(df, z, out, sums, 1, work)
         return out
@@ -321,13 +325,16 @@ def gelu_bwd16(df: torch.Tensor, z: torch.Tensor, sums: Optional[torch.Tensor] =
     return out
 
 
-def rows_scale_add(a: Optional[torch.Tensor], b: torch.Tensor, scale: torch.Tensor, rows_per_group: int, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
-    """out = a + scale[row // rows_per_group] * b (a None: the scaled b alone) - fp32 (rows, cols) inputs, scale fp32 (groups); DropPath."""
-    _need_cuda(a, b, scale)
+def rows_scale_add(a: Optional[torch.Tensor], b: torch.Tensor, scale: torch.Tensor, rows_per_group: int, out_dtype: torch.dtype = torch.float32,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = a + scale[row // rows_per_group] * b (a None: the scaled b alone) - fp32 (rows, cols) inputs, scale fp32 (groups); DropPath.
+    `out` may be given (contiguous, `out_dtype`)."""
+    _need_cuda(a, b, scale, out)
     rows, cols = b.shape
     assert b.dtype == scale.dtype == torch.float32 and b.is_contiguous() and scale.is_contiguous() and scale.numel() * rows_per_group == rows
     assert a is None or (a.dtype == torch.float32 and a.shape == b.shape and a.is_contiguous())
-    out = torch.empty((rows, cols), dtype=out_dtype, device=b.device)
+    out = torch.empty((rows, cols), dtype=out_dtype, device=b.device) if out is None else out
+    assert out.dtype == out_dtype and out.shape == (rows, cols) and out.is_contiguous()
     _lib.check(_lib.load().cir_rows_scale_add(_ptr(a), b.data_ptr(), scale.data_ptr(), out.data_ptr(), rows, cols, int(rows_per_group), _DT[out_dtype],
                                               _stream()), "cir_rows_scale_add")
     return out

@@ -149,9 +149,10 @@ def check(case, outputs, ref=None, bnd=None):
     return fails
 
 
-def worst_ratio(case, outputs):
+def worst_ratio(case, outputs, ref=None, bnd=None):
     """max |out - ref| / bound over the bounded outputs (for printing next to an assertion)."""
-    ref, bnd = ref64(case), bound(case)
+    ref = ref64(case) if ref is None else ref
+    bnd = bound(case) if bnd is None else bnd
     w = 0.0
     for name, out in outputs.items():
         if bnd[name] is not None:
@@ -511,6 +512,17 @@ def _erf_terms(x):
     return erf, e_erf
 
 
+def gelu_bwd_terms(x, d):
+    """(float64 d * gelu'(x), its fp32 bound) on float64 operands: the gelu' terms of the module docstring (shared with tests/rowpass_cases.py)."""
+    erf, e_erf = _erf_terms(x)
+    a = 0.5 * x * x
+    xphi = x.abs() * torch.exp(-a) / math.sqrt(2 * math.pi)
+    gp = 0.5 * (1 + erf) + x * torch.exp(-a) / math.sqrt(2 * math.pi)
+    e_gp = (e_erf + U * (1 + erf).abs()) / 2 + xphi * ((4 * a + 4) * U + 3 * U) + 2.0 ** -126 * x.abs() + U * gp.abs()
+    y = d * gp
+    return y, d.abs() * e_gp + U * y.abs()
+
+
 def _eltwise_terms(c):
     """(float64 result, fp32 bound or None)."""
     i = inputs(c)
@@ -520,13 +532,7 @@ def _eltwise_terms(c):
         y = 0.5 * x * (1 + erf)
         return y, x.abs() / 2 * (e_erf + U * (1 + erf).abs()) + 2 * U * y.abs()
     if c.mode == "gelu_bwd":
-        erf, e_erf = _erf_terms(x)
-        a = 0.5 * x * x
-        xphi = x.abs() * torch.exp(-a) / math.sqrt(2 * math.pi)
-        gp = 0.5 * (1 + erf) + x * torch.exp(-a) / math.sqrt(2 * math.pi)
-        e_gp = (e_erf + U * (1 + erf).abs()) / 2 + xphi * ((4 * a + 4) * U + 3 * U) + 2.0 ** -126 * x.abs() + U * gp.abs()
-        y = d * gp
-        return y, d.abs() * e_gp + U * y.abs()
+        return gelu_bwd_terms(x, d)
     if c.mode == "relu":
         return x.clamp_min(0.0), None
     if c.mode == "relu_bwd":
