@@ -48,6 +48,8 @@ def init_tokenizer(vocab_file: Optional[str] = None, allow_fallback: bool = Fals
 
 
 def create_vit(vit: str, image_size: int, use_grad_checkpointing: bool = False, ckpt_layer: int = 0, drop_path_rate: float = 0):
-    """Geometry of the reference's ViT factory (blip.py:194-209); gradient checkpointing / DropPath are training-only."""
+    """Geometry of the reference's ViT factory (blip.py:194-209).  `use_grad_checkpointing` / `ckpt_layer` are carried by the MODEL, not by
+    the geometry: `BLIP_NLVR` / `BLIP_Retrieval` keep their `vit_grad_ckpt` / `vit_ckpt_layer` and checkpoint the last min(ckpt_layer, depth)
+    blocks of the ViT's training pass (`set_vit_checkpointing`; vit.py:103-105, :158) - pass them there.  DropPath is training-only."""
     g = VitGeometry.named(vit, image_size)
     return g, g.width

@@ -37,6 +37,7 @@ class BLIP_Retrieval(_EngineHost):
         # blip_stage1.py:34 passes create_vit no drop_path_rate: the stage-I image encoder has no DropPath (the stage-II one has 0.1) - a
         # copy, so that a geometry object shared with a stage-II model keeps its rate
         self.vit_geometry = dataclasses.replace(vit_geometry or VitGeometry.named(vit, image_size), drop_path_rate=0.0)
+        self._keep_vit_checkpointing(vit_grad_ckpt, vit_ckpt_layer)            # blip_stage1.py:34
         self.image_tuning = False              # `set_image_tuning`: image features with a graph in .train() mode (--blip-img-tune); off by default
         self.bert_geometry = load_bert_geometry(med_config)
         self.bert_geometry.encoder_width = self.vit_geometry.width

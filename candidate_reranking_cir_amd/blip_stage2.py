@@ -124,8 +124,28 @@ class _EngineHost(nn.Module):
                                                # query-side fold instead of the projected K|V path (`set_long_caption_fold_wide`; off by default)
         self.short_caption_fold = False        # two-branch encoder: captions of at most 16 tokens take the one-block query-side fold instead of the
                                                # 32-token kernels (`set_short_caption_fold`; off by default)
+        self.vit_grad_ckpt, self.vit_ckpt_layer = False, 0      # what the factory was given (blip.py:194-209 hands them to the ViT)
+        self.vit_ckpt_blocks = 0               # trailing ViT blocks whose activations the training backward recomputes (`set_vit_checkpointing`)
         self.graph_candidates = 0              # `score` calls with at most this many candidate rows replay a captured HIP graph per
                                                # shape (0 = off; `enable_graphs`): single-query serving is launch-bound from the host
+
+    def _keep_vit_checkpointing(self, vit_grad_ckpt, vit_ckpt_layer):
+        """The factory's two arguments (vit.py:158: block i is wrapped iff use_grad_checkpointing and i >= depth - ckpt_layer)."""
+        self.vit_grad_ckpt, self.vit_ckpt_layer = bool(vit_grad_ckpt), int(vit_ckpt_layer)
+        return self.set_vit_checkpointing(self.vit_ckpt_layer if self.vit_grad_ckpt else 0)
+
+    def set_vit_checkpointing(self, n: int):
+        """Gradient checkpointing of the image encoder's training pass (`vit_grad_ckpt` / `vit_ckpt_layer` of the factories; fairscale's
+        checkpoint_wrapper around attn and mlp of the last `ckpt_layer` blocks in the reference, vit.py:103-105, :158): the last
+        min(n, depth) blocks keep only their two fp32 stream rows for the backward (6144 of 30768 bytes per token and block at width 768),
+        which rebuilds their activations with the forward's own launches before their adjoints (`train_vit.VitTrainer`).  Tokens and, in the
+        deterministic mode, gradients are bit-identical to the unchecked pass.  0 (the default) checkpoints nothing.  Read at every
+        train-mode `img_embed` call; a call already made keeps the form it saved.  `train.vit_saved_bytes` gives the bytes per call."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"set_vit_checkpointing: {n} blocks")
+        self.vit_ckpt_blocks = min(n, self.vit_geometry.depth)
+        return self
 
     @property
     def stream_dtype(self) -> torch.dtype:
@@ -289,6 +309,7 @@ class BLIP_NLVR(_EngineHost):
                  vit_geometry: Optional[VitGeometry] = None, tokenizer=None, fold_merge: bool = True):
         super().__init__()
         self.vit_geometry = vit_geometry or VitGeometry.named(vit, image_size)
+        self._keep_vit_checkpointing(vit_grad_ckpt, vit_ckpt_layer)         # blip_stage2.py:37
         self.bert_geometry = load_bert_geometry(med_config)
         self.bert_geometry.encoder_width = self.vit_geometry.width          # blip_stage2.py:47
         self.fold_merge = fold_merge

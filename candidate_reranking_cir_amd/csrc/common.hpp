@@ -87,6 +87,8 @@ __device__ __forceinline__ float fast_erf(float x) {
 }
 __device__ __forceinline__ float gelu_erf_as(float x) { return 0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752f)); }   // (scalar form of gelu_erf_as8: tools / reference for it)
 
+// the exact erf-GELU, ACT2FN['gelu'] / nn.GELU as written (the training pass: cir_eltwise mode 0 in train.hip, cir_rows16_gelu_pair in train_fused.hip)
+__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 // d/dx of the exact erf-GELU (the training pass: cir_eltwise mode 1 in train.hip, cir_rows16_colsum mode 1 in train_fused.hip)
 __device__ __forceinline__ float gelu_grad(float x) {
     return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);

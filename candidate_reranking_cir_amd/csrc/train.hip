@@ -186,7 +186,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* x, cons
 }
 
 // ---- elementwise ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 // mode 0: y = gelu(z); 1: dz = dy * gelu'(z); 2: y = relu(z); 3: dz = dy * (z > 0); 4: y = dropout(z) [dy unused]; 5: y = z + dy (add);
 // 6: y = p_drop * z (scale by the factor passed in p_drop)
 // (Tried in round 4: the logistic-fit GELU of the inference epilogue for 16-bit outputs - the 2R x 3072 pass went 58 -> 54 us, it is bound

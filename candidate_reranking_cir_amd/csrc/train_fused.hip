@@ -245,6 +245,56 @@ __global__ __launch_bounds__(256) void rows16_colsum_kernel(const T* a, int64_t 
     }
 }
 
+// ---- 16-bit rows: dz = a * gelu'(z) AND f = gelu(z) from one read of z, with the column sums of dz --------------------------------------
+// The backward of a CHECKPOINTED ViT block (vit.py:36-37, 103-105): gelu(z) was released with the forward, and fc2's weight gradient wants
+// it back as its left operand.  z (3072 / 4096 columns) is the widest tensor of the block; this pass reads it anyway for dz.  Same block
+// shape and the same reduction as rows16_colsum_kernel MODE 1 (whose dz and sums it reproduces bit for bit), gelu_exact as cir_eltwise
+// mode 0 evaluates it.  ORD: `sums` is the partial workspace, the block stores to its row blockIdx.y.
+template <typename T, bool ORD>
+__global__ __launch_bounds__(256) void rows16_gelu_pair_kernel(const T* a, int64_t lda, const T* z, int64_t ldz, T* out, int64_t ldo, T* outf, int64_t ldf,
+                                                               float* sums, int64_t rows, int cols) {
+    typedef typename Elem<T>::x8 X8;
+    const int cg = threadIdx.x & 31, rl = threadIdx.x >> 5;
+    const int c = (blockIdx.x * 32 + cg) * 8;
+    const int64_t r0 = (int64_t)blockIdx.y * 64;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+    if (c < cols) {
+#pragma unroll 2
+        for (int it = 0; it < 8; ++it) {
+            const int64_t r = r0 + it * 8 + rl;
+            if (r >= rows) break;
+            const X8 av = *reinterpret_cast<const X8*>(a + r * lda + c);
+            const X8 zv = *reinterpret_cast<const X8*>(z + r * ldz + c);
+            X8 o, f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float zf = static_cast<float>(zv[e]);
+                const float v = static_cast<float>(av[e]) * gelu_grad(zf);
+                o[e] = static_cast<T>(v);
+                acc[e] += v;
+                f[e] = static_cast<T>(gelu_exact(zf));
+            }
+            *reinterpret_cast<X8*>(out + r * ldo + c) = o;
+            *reinterpret_cast<X8*>(outf + r * ldf + c) = f;
+        }
+    }
+    if (sums == nullptr) return;
+    __shared__ float red[8][256 + 8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[rl][cg * 8 + e] = acc[e];
+    __syncthreads();
+    const int cc = blockIdx.x * 256 + threadIdx.x;
+    if (cc < cols) {
+        float v = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v += red[j][threadIdx.x];
+        if constexpr (ORD) sums[(int64_t)blockIdx.y * cols + cc] = v;
+        else atomicAdd(sums + cc, v);
+    }
+}
+
 // ---- out = a + s[row / rows_per_group] * b : a per-GROUP scale of a branch added to the stream (DropPath: timm's per-sample stochastic
 // depth, vit.py:98-109), or with a = NULL the scaled branch gradient written as the 16-bit operand of the adjoint products
 template <typename TO>
@@ -398,4 +448,45 @@ extern "C" int cir_rows16_colsum_ordered(const void* a, int64_t lda, const void*
                                          int cols, int mode, int dtype, float* partials, int64_t partial_elems, void* stream) {
     CIR_CHECK_PTR(sums); CIR_CHECK_PTR(partials);
     return rows16_colsum(a, lda, z, ldz, out, ldo, sums, rows, cols, mode, dtype, partials, partial_elems, stream);
+}
+
+// The pair pass of a checkpointed ViT block: argument checks of the rows16 family, then one launch (+ the finishing sum of the ordered form)
+static int rows16_gelu_pair(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, void* out_f, int64_t ldf, float* sums,
+                            int64_t rows, int cols, int dtype, bool ord, float* partials, int64_t partial_elems, void* stream) {
+    CIR_CHECK_PTR(a); CIR_CHECK_PTR(z); CIR_CHECK_PTR(out); CIR_CHECK_PTR(out_f);
+    if (ord) CIR_CHECK_PTR(partials);
+    if (rows <= 0 || cols <= 0) return CIR_EINVAL;
+    if (cols % 8 != 0) return CIR_ESHAPE;
+    if (lda % 8 != 0 || ldz % 8 != 0 || ldo % 8 != 0 || ldf % 8 != 0) return CIR_EALIGN;
+    if (lda < cols || ldz < cols || ldo < cols || ldf < cols) return CIR_ESHAPE;
+    if (dtype != CIR_BF16 && dtype != CIR_F16) return CIR_EDTYPE;
+    if (!cir_aligned16(a) || !cir_aligned16(z) || !cir_aligned16(out) || !cir_aligned16(out_f)) return CIR_EALIGN;
+    const int64_t row_blocks = (rows + 63) / 64;
+    if (row_blocks > 65535) return CIR_ESHAPE;
+    ord = ord && sums != nullptr;                                              // no sums wanted: nothing to order
+    if (ord && partial_elems < row_blocks * cols) return CIR_ESHAPE;
+    dim3 grid((cols + 255) / 256, (unsigned)row_blocks), block(256);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    by_dtype16(dtype, [&](auto t) { by_bool(ord, [&](auto od) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((rows16_gelu_pair_kernel<T, decltype(od)::value>), grid, block, 0, s, reinterpret_cast<const T*>(a), lda,
+                           reinterpret_cast<const T*>(z), ldz, reinterpret_cast<T*>(out), ldo, reinterpret_cast<T*>(out_f), ldf, ord ? partials : sums,
+                           rows, cols);
+    }); });
+    if (!ord) CIR_LAUNCH_RESULT();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    OrderedDst d{};
+    d.out[0] = sums; d.nout = 1;
+    return colsum_ordered_launch(partials, cols, row_blocks, cols, d, s);
+}
+
+extern "C" int cir_rows16_gelu_pair(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, void* out_f, int64_t ldf,
+                                    float* sums, int64_t rows, int cols, int dtype, void* stream) {
+    return rows16_gelu_pair(a, lda, z, ldz, out, ldo, out_f, ldf, sums, rows, cols, dtype, false, nullptr, 0, stream);
+}
+
+extern "C" int cir_rows16_gelu_pair_ordered(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, void* out_f, int64_t ldf,
+                                            float* sums, int64_t rows, int cols, int dtype, float* partials, int64_t partial_elems, void* stream) {
+    return rows16_gelu_pair(a, lda, z, ldz, out, ldo, out_f, ldf, sums, rows, cols, dtype, true, partials, partial_elems, stream);
 }

@@ -39,6 +39,7 @@ from .train_core import (Trainer, _Lin, _Lin2, _cast, _install_grads, _row_split
                          loss_scale, train_dtype, training_state)                                                             # (re-exported)
 from .train_optim import AdamW, cosine_lr_schedule  # noqa: F401  (re-exported)
 from .train_ops import deterministic, set_deterministic  # noqa: F401  (re-exported: the deterministic training mode)
+from .train_vit import vit_checkpointed_blocks, vit_saved_bytes  # noqa: F401  (re-exported: ViT gradient checkpointing)
 
 
 class NlvrTrainer(Trainer):

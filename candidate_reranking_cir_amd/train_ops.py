@@ -325,6 +325,29 @@ def gelu_bwd16(df: torch.Tensor, z: torch.Tensor, sums: Optional[torch.Tensor] =
     return out
 
 
+def gelu_bwd16_pair(df: torch.Tensor, z: torch.Tensor, sums: Optional[torch.Tensor] = None, work: Optional[Workspace] = None,
+                    out: Optional[torch.Tensor] = None, out_f: Optional[torch.Tensor] = None):
+    """(dz, f) = (df * gelu'(z), gelu(z)) on 16-bit (rows, cols) tensors from ONE read of z (cir_rows16_gelu_pair: the backward of a
+    checkpointed ViT block, whose gelu(z) went with the forward); dz and the column sums added to `sums` are `gelu_bwd16`'s bit for bit,
+    f is `eltwise(z, MODE_GELU)`'s.  `work`: the sums in the fixed order of cir_rows16_gelu_pair_ordered.  `out` / `out_f` may be given
+    (unit last stride, row stride a multiple of 8)."""
+    _need_cuda(df, z, sums, out, out_f)
+    assert df.dim() == 2 and df.shape == z.shape and df.dtype == z.dtype and df.stride(1) == 1 and z.stride(1) == 1
+    assert sums is None or (sums.dtype == torch.float32 and sums.shape == (df.shape[1],) and sums.is_contiguous())
+    out = torch.empty(df.shape, dtype=df.dtype, device=df.device) if out is None else out
+    out_f = torch.empty(df.shape, dtype=df.dtype, device=df.device) if out_f is None else out_f
+    for o in (out, out_f):
+        assert o.shape == df.shape and o.dtype == df.dtype and o.stride(1) == 1 and o.stride(0) % 8 == 0
+    args = (df.data_ptr(), df.stride(0), z.data_ptr(), z.stride(0), out.data_ptr(), out.stride(0), out_f.data_ptr(), out_f.stride(0), _ptr(sums),
+            df.shape[0], df.shape[1], _DT[df.dtype])
+    if work is not None and sums is not None:
+        part = work.f32((df.shape[0] + 63) // 64 * df.shape[1], df.device)
+        _lib.check(_lib.load().cir_rows16_gelu_pair_ordered(*args, part.data_ptr(), part.numel(), _stream()), "cir_rows16_gelu_pair_ordered")
+    else:
+        _lib.check(_lib.load().cir_rows16_gelu_pair(*args, _stream()), "cir_rows16_gelu_pair")
+    return out, out_f
+
+
 def rows_scale_add(a: Optional[torch.Tensor], b: torch.Tensor, scale: torch.Tensor, rows_per_group: int, out_dtype: torch.dtype = torch.float32,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = a + scale[row // rows_per_group] * b (a None: the scaled b alone) - fp32 (rows, cols) inputs, scale fp32 (groups); DropPath.

@@ -13,6 +13,11 @@ dropout: the dropout-free instantiations), the four weight gradients of a block 
 in flat buffers (`train_core._Slab`; the machinery the passes share is in train_core.py) so that `train.AdamW` updates the ViT in one
 launch.  Pre-LayerNorm blocks: x + f(LayerNorm(x)), so the LayerNorm adjoint's input is the saved residual stream itself and its result is
 added to the skip gradient.
+
+Gradient checkpointing (`vit_grad_ckpt` / `vit_ckpt_layer` of the factories, `set_vit_checkpointing`; fairscale's checkpoint_wrapper around
+attn and mlp of block i >= depth - ckpt_layer in the reference, vit.py:103-105, :158): such a block keeps only x and x1, the two fp32 stream
+rows its LayerNorm adjoints read, and `backward` rebuilds the rest by the forward's own launches (`_recompute`) before the block's adjoints;
+gelu(fc1's output), the left operand of fc2's weight gradient, comes from the pass that reads fc1's output for dz (`gelu_bwd16_pair`).
 """
 from __future__ import annotations
 
@@ -25,6 +30,35 @@ from . import ops, train_ops as T
 from .train_core import _LN, Trainer, _cast, _install_grads, apply_pending_counters, loss_scale
 
 _P = "visual_encoder."
+
+
+def vit_checkpointed_blocks(model) -> int:
+    """Number of trailing ViT blocks whose activations are recomputed in the backward: 0 unless the factory was given `vit_grad_ckpt`, else
+    min(vit_ckpt_layer, depth) (`set_vit_checkpointing` changes it) - block i is checkpointed iff i >= depth - that number (vit.py:158)."""
+    return max(0, min(int(getattr(model, "vit_ckpt_blocks", 0)), model.vit_geometry.depth))
+
+
+def _block_saved_bytes(geo, ckpt: bool) -> int:
+    """Bytes per token a block keeps for its backward: an unchecked block's ten tensors (x, x1, ctx32 fp32 and h16, ctx, h2 16-bit of width
+    D; qkv 16-bit of 3 D; z16, f16 16-bit of the MLP width; lse fp32 per head - 30768 at width 768), a checkpointed block's x and x1 (6144)."""
+    d = geo.width
+    if ckpt:
+        return 2 * 4 * d
+    return 3 * 4 * d + 2 * (3 * d + 3 * d + 2 * geo.mlp_ratio * d) + 4 * geo.num_heads
+
+
+def vit_saved_bytes(model, batch: int) -> int:
+    """Bytes one `img_embed(image)` call of `batch` images in train mode keeps for its backward under the model's current checkpointing
+    setting: the summed `nbytes` of the tensors of the call's saved state - the 16-bit patch rows, each block's entry (`VitTrainer.forward`),
+    the final fp32 stream and, where the geometry has DropPath, the call's (depth, 2, batch) fp32 scales.  From the geometry and the operand
+    type (16-bit in every mode, `vit_train_dtype`) alone: no device access."""
+    geo = model.vit_geometry
+    n, depth = geo.num_tokens, geo.depth
+    ck = vit_checkpointed_blocks(model)
+    patch_cols = geo.in_chans * geo.patch_size * geo.patch_size
+    per_token = (depth - ck) * _block_saved_bytes(geo, False) + ck * _block_saved_bytes(geo, True) + 4 * geo.width
+    drop_path = 4 * depth * 2 if float(getattr(geo, "drop_path_rate", 0.0)) > 0.0 and depth >= 2 else 0
+    return int(batch) * ((n - 1) * patch_cols * 2 + n * per_token + drop_path)
 
 
 def vit_train_dtype(model) -> torch.dtype:
@@ -96,7 +130,10 @@ class VitTrainer(Trainer):
         # What the reverse pass needs travels WITH THE CALL (the autograd node keeps it), not on the trainer: the reference embeds the
         # reference and the target images in `blip_bs` mini-batches, every call with a graph (stage2_train.py:191-199) - several calls
         # are live at once, and each backward must find its own activations and its own DropPath draw (round-4 advisor finding).
-        sv = {"patches": patches, "bsz": bsz, "blocks": [], "dp": dp, "dp_rates": dp_rates, "epoch": _lib.PARAM_EPOCH[0]}
+        # Gradient checkpointing (vit.py:103-105, :158): the setting is read HERE, once per call, and the form each block saved is recorded
+        # beside its entry - the backward follows the record, whatever the setting has become by then.
+        first_ckpt = len(self.blocks) - vit_checkpointed_blocks(self.model)
+        sv = {"patches": patches, "bsz": bsz, "blocks": [], "ckpt": [], "dp": dp, "dp_rates": dp_rates, "epoch": _lib.PARAM_EPOCH[0]}
         heads = lambda t, j: self._heads(t, bsz, n, j, 3)
 
         def branch(lin, a16, res, i, j):
@@ -116,12 +153,41 @@ class VitTrainer(Trainer):
             z16 = blk["fc1"].fwd(h2, dt)                                             # vit.py:36
             f16 = T.eltwise(z16, T.MODE_GELU, out_dtype=dt)                         # vit.py:37
             x2 = branch(blk["fc2"], f16, x1, i, 1)                                  # vit.py:39, :109
-            sv["blocks"].append(dict(x=x, h16=h16, qkv=qkv, ctx=ctx, ctx32=ctx32, lse=lse, x1=x1, h2=h2, z16=z16, f16=f16))
+            ckpt = i >= first_ckpt
+            sv["ckpt"].append(ckpt)
+            if ckpt:                                                                 # the two fp32 stream rows the LayerNorm adjoints read; the rest goes now
+                sv["blocks"].append(dict(x=x, x1=x1))
+            else:
+                sv["blocks"].append(dict(x=x, h16=h16, qkv=qkv, ctx=ctx, ctx32=ctx32, lse=lse, x1=x1, h2=h2, z16=z16, f16=f16))
             x = x2
         sv["xf"] = x
         y32, _ = self.lnf.fwd(x, dt)                                                 # vit.py:192
         self.sv = sv                                                                 # (the latest call's state: tests / tools read it)
         return y32.view(bsz, n, d), sv
+
+    # ------------------------------------------------------------------------------------------------ recompute
+    def _recompute(self, blk: Dict, s: Dict, bsz: int, n: int):
+        """The activations of a checkpointed block from its saved x and x1, by the launches (kernels and arguments) `forward` made: both
+        LayerNorms, the qkv and fc1 products, the attention.  The proj and fc2 products are not needed again (x1 and the next block's x
+        are saved); no random number is drawn (DropPath acts outside the two sub-modules, its scales travel with the call).  f16 = gelu(z16)
+        comes back EMPTY where fc2's weight gradient is a queued product: `gelu_bwd16_pair` fills it in the pass that reads z16 for dz,
+        before the block's grouped weight-gradient launch reads it.  Returns (the full entry, whether f16 is still to be filled)."""
+        dt, d, f32 = self.dtype, self.geo.width, torch.float32
+        x, x1 = s["x"], s["x1"]
+        heads = lambda t, j: self._heads(t, bsz, n, j, 3)
+        _, h16 = self._ln16(blk["ln1"], x)
+        qkv = blk["qkv"].fwd(h16, dt)
+        ctx = torch.empty((bsz * n, d), dtype=dt, device=x.device)
+        ctx32 = torch.empty((bsz * n, d), dtype=f32, device=x.device)
+        lse = T.attention_train_fwd(heads(qkv, 0), heads(qkv, 1), heads(qkv, 2), None, self._heads(ctx, bsz, n), self._scale, 0.0, 0,
+                                    out32=self._heads(ctx32, bsz, n))
+        _, h2 = self._ln16(blk["ln2"], x1)
+        z16 = blk["fc1"].fwd(h2, dt)
+        # `_Lin.bwd16` reads its left operand at once unless it queues the product (both extents multiples of 128, train_wgrad.hip): then
+        # - every real width - the pair kernel may deliver f16 later; otherwise it is recomputed here, by the forward's own launch
+        pair = blk["fc2"].n % 128 == 0 and blk["fc2"].k % 128 == 0
+        f16 = torch.empty_like(z16) if pair else T.eltwise(z16, T.MODE_GELU, out_dtype=dt)
+        return dict(x=x, h16=h16, qkv=qkv, ctx=ctx, ctx32=ctx32, lse=lse, x1=x1, h2=h2, z16=z16, f16=f16), pair
 
     # ------------------------------------------------------------------------------------------------ backward
     @torch.no_grad()
@@ -165,12 +231,17 @@ class VitTrainer(Trainer):
             """The stream gradient as the branch's 16-bit operand: scaled per sample where block i drops samples."""
             return _cast(gq, dt) if dp is None or dp_rates[i] <= 0.0 else T.rows_scale_add(None, gq, dp[i, j], n, out_dtype=dt)
         for i in reversed(range(len(self.blocks))):
-            blk, s = self.blocks[i], sv["blocks"][i]
+            blk, s, pair = self.blocks[i], sv["blocks"][i], False
             wq: list = []
+            if sv["ckpt"][i]:
+                s, pair = self._recompute(blk, s, bsz, n)
             # x2 = x1 + DropPath(fc2(gelu(fc1(LayerNorm2(x1)))))
             g16 = branch_grad(g, i, 1)
             df16 = blk["fc2"].bwd16(s["f16"], g16, dx_dtype=dt, bias=True, queue=wq)
-            dz16 = T.gelu_bwd16(df16, s["z16"], sums=blk["fc1"].db, **det)
+            if pair:                                                                 # dz and the f16 the queued fc2 weight gradient reads, one pass over z16
+                dz16, _ = T.gelu_bwd16_pair(df16, s["z16"], sums=blk["fc1"].db, out_f=s["f16"], **det)
+            else:
+                dz16 = T.gelu_bwd16(df16, s["z16"], sums=blk["fc1"].db, **det)
             dh2 = blk["fc1"].bwd16(s["h2"], dz16, queue=wq)                         # (B N, D) fp32
             g = T.eltwise(blk["ln2"].bwd_res(s["x1"], dh2, dt, want_dt=False)[0], T.MODE_ADD, g)
             # x1 = x + DropPath(proj(attention(LayerNorm1(x))))
@@ -183,6 +254,7 @@ class VitTrainer(Trainer):
             dh = blk["qkv"].bwd16(s["h16"], dqkv16, bias=True, queue=wq)
             g = T.eltwise(blk["ln1"].bwd_res(s["x"], dh, dt, want_dt=False)[0], T.MODE_ADD, g)
             self._wgrad_grouped(wq)
+            s = wq = None                                                            # a recomputed block's tensors go before the next block's arrive
         # x0 = cat(cls, patch_embed(image)) + pos_embed (vit.py:182-187)
         g3 = g.view(bsz, n, d)
         T.colsum(g.view(bsz, n * d), self.dpos.reshape(-1), **det)

@@ -496,6 +496,14 @@ int cir_layernorm_bwd_fused(const float* x, const float* gamma, const float* dy,
  * sums[c] += sum_r out[r][c] - BertIntermediate's adjoint (nlvr_encoder.py:383-396) with the bias gradient in the same pass. */
 int cir_rows16_colsum(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, float* sums, int64_t rows, int cols, int mode,
                       int dtype, void* stream);
+/* The backward of a gradient-CHECKPOINTED ViT block (vit.py:36-37: Mlp.forward's fc1 -> act; vit.py:103-105: attn / mlp of block i wrapped in
+ * checkpoint_wrapper when use_grad_checkpointing and i >= depth - ckpt_layer): gelu(z) was released with the forward and fc2's weight gradient
+ * wants it back.  One pass over a (= d gelu(z)) and z writes BOTH  out = a * gelu'(z)  (bit-identical to cir_rows16_colsum mode 1, and so are
+ * the sums)  and  out_f = gelu(z)  (bit-identical to cir_eltwise mode 0 on the same z), and, when sums is given, sums[c] += sum_r out[r][c].
+ * 16-bit rows (rows, cols), cols % 8 == 0 (CIR_ESHAPE); row strides lda / ldz / ldo / ldf multiples of 8 elements and all four pointers
+ * 16-byte aligned (CIR_EALIGN); dtype CIR_BF16 / CIR_F16; a, z, out, out_f required (CIR_EINVAL), sums may be NULL. */
+int cir_rows16_gelu_pair(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, void* out_f, int64_t ldf, float* sums,
+                         int64_t rows, int cols, int dtype, void* stream);
 /* out[r] = a[r] + scale[r / rows_per_group] * b[r] over rows of `cols` fp32 values (a may be NULL: out = scale * b); out fp32 or 16-bit
  * (out_dtype).  DropPath - timm's per-sample stochastic depth around both branches of a ViT block (vit.py:98-109; blip_stage2.py:37 builds the
  * stage-II image encoder with drop_path_rate 0.1) - in the ViT fine-tuning pass: the forward adds the sample-scaled branch to the stream, the
@@ -542,6 +550,11 @@ int cir_layernorm_bwd_fused_ordered(const float* x, const float* gamma, const fl
  * finishing sum.  partial_elems >= ceil(rows / 64) * cols.  `out` (mode 1) is bit-identical to the plain form's. */
 int cir_rows16_colsum_ordered(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, float* sums, int64_t rows, int cols,
                               int mode, int dtype, float* partials, int64_t partial_elems, void* stream);
+/* cir_rows16_gelu_pair (vit.py:36-37, 103-105) with the sums in the fixed order of cir_rows16_colsum_ordered (the same workgroups, the same
+ * partials, the same finishing sum: the same bits as its mode 1).  partials is required, partial_elems >= ceil(rows / 64) * cols when sums
+ * is given; with sums NULL no sum is formed.  out / out_f are bit-identical to the plain form's. */
+int cir_rows16_gelu_pair_ordered(const void* a, int64_t lda, const void* z, int64_t ldz, void* out, int64_t ldo, void* out_f, int64_t ldf, float* sums,
+                                 int64_t rows, int cols, int dtype, float* partials, int64_t partial_elems, void* stream);
 /* cir_embed_bwd in a fixed order; ids outside [0, table_rows) are skipped.
  * dword: the rows are cut into chunks of 512.  Inside a chunk the rows of one id are added in ascending row order, starting from the first
  * of them.  With one chunk that sum is added to dword[id].  Otherwise the chunk sums of an id are added in ascending chunk order, starting
