@@ -274,7 +274,38 @@ class _EngineHost(nn.Module):
         `train.AdamW.step` and `load_state_dict` of the model or any submodule are followed without it."""
         self._weights_epoch += 1
         self._param_lists = None
+        for twin in tuple(self.__dict__.get("_twins") or ()):
+            twin.invalidate_packed_weights()
         return self
+
+    _TWIN_FRESH = ("_trainer", "_vit_trainer", "_med_dropout", "_packed_key", "_packed_keys", "_twins", "_pending_counters")    # per-model caches a twin starts without
+
+    def referee(self):
+        """A model of the same class and geometry over the SAME `Parameter` objects, in the "exact" precision with packed engines of its
+        own: the referee of rank refinement (`validate_stage2.refine_predictions`).  No second fp32 copy of the weights exists, and the
+        twin's `weights_key` reads the same version counters, so every write the primary's packed copies follow - in-place torch ops,
+        optimizer steps, `train.AdamW.step`, a copying `load_state_dict` - repacks the twin as well; `invalidate_packed_weights()` and
+        `.to()` / `.float()` on the primary reach its live twins (held weakly).  The primary's precision, engines, graphs and switches
+        are untouched; the twin's switches are its own.  The module tree is the twin's own, so `load_state_dict(assign=True)` on either
+        side - which replaces Parameter objects - BREAKS the sharing: build a new referee afterwards.  Every call returns a new twin."""
+        import weakref
+
+        def clone(mod):
+            new = mod.__class__.__new__(mod.__class__)
+            for k, val in mod.__dict__.items():                      # containers (parameters, buffers, hooks) are the twin's own; what they hold is shared
+                new.__dict__[k] = type(val)(val) if isinstance(val, dict) else val
+            new.__dict__["_modules"] = type(mod._modules)((name, clone(child)) for name, child in mod._modules.items())
+            return new
+
+        twin = clone(self)
+        for k in self._TWIN_FRESH:
+            twin.__dict__.pop(k, None)
+        twin._engines, twin._param_lists, twin._lists_epoch, twin.graph_candidates = None, None, -1, 0
+        twin.set_precision("exact")
+        if self.__dict__.get("_twins") is None:
+            self.__dict__["_twins"] = weakref.WeakSet()
+        self._twins.add(twin)
+        return twin
 
     def _part_params(self, part: str):
         if not self._loads_hooked:                 # load_state_dict(assign=True) of a submodule replaces Parameter objects: new list

@@ -9,6 +9,10 @@
 // LDS and keeps its first k (value, column) pairs; level 2 sorts groups of floor(8192 / k) such lists the same way until one is left.
 // Lists are always k pairs long: missing places hold the padding pair (-inf, INT_MAX), which comes after every real column (columns are
 // below 2^31 - 1) and never reaches the result, because k <= n - 1 real columns exist in every row.
+//
+// Rank refinement (cir_rank_undecided, cir_rank_refine_apply; validate_stage2.py:53, 174, 188): the same sort and order, on rows of at most
+// 8192 logits of a fast precision mode - which entries lie within 2 * margin of a neighbour of the sorted row, so that only they are scored
+// again by the exact mode, and the write-back of those scores with a check of the margin on the values they replace.
 #include "common.hpp"
 
 namespace cir {
@@ -185,6 +189,149 @@ __global__ __launch_bounds__(256) void rank_of_kernel(const float* __restrict__ 
     }
 }
 
+// ---- rank refinement: which entries of a row of fast logits can the fast mode not order? (validate_stage2.py:53, 174, 188) ----
+// One workgroup per row sorts the whole row (rank_sort_first with first = n_pow2) and links neighbours of the sorted row whose fp32 difference
+// is at most `width` = 2 * margin; an entry linked to either neighbour is undecided.  flags[row * K + column] receives 1 / 0 for every column
+// (an inactive row: all 0), row_count[row] the number of ones.  The padding pairs sort behind all K real ones, so places 0 .. K - 1 are real
+// and every column written is below K.  A difference that is not a number (-inf against -inf: NaN keys, the padding) fails `<=` and links nothing.
+__global__ __launch_bounds__(1024) void undecided_flag_kernel(const float* __restrict__ values, int64_t ld, const unsigned char* __restrict__ active,
+                                                              float width, int K, unsigned char* __restrict__ flags, int* __restrict__ row_count) {
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    RankPair* p = reinterpret_cast<RankPair*>(dyn);
+    const int64_t row = blockIdx.x;
+    unsigned char* f = flags + row * K;
+    if (active != nullptr && active[row] == 0) {                       // uniform over the workgroup: nobody reaches a barrier
+        for (int i = threadIdx.x; i < K; i += blockDim.x) f[i] = 0;
+        if (threadIdx.x == 0) row_count[row] = 0;
+        return;
+    }
+    int n_pow2 = 2;
+    while (n_pow2 < K) n_pow2 <<= 1;
+    const float* src = values + row * ld;
+    for (int i = threadIdx.x; i < n_pow2; i += blockDim.x) {
+        RankPair e;
+        if (i < K) { e.v = rank_key(src[i]); e.i = i; }
+        else { e.v = -INFINITY; e.i = RANK_PAD; }
+        p[i] = e;
+    }
+    __syncthreads();
+    rank_sort_first(p, n_pow2, n_pow2);
+    int mine = 0;
+    for (int j = threadIdx.x; j < K; j += blockDim.x) {
+        const RankPair e = p[j];
+        bool und = false;
+        if (j > 0) und = (p[j - 1].v - e.v) <= width;
+        if (j + 1 < K) und = und || ((e.v - p[j + 1].v) <= width);
+        f[e.i] = und ? 1 : 0;
+        mine += und ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    __syncthreads();                                                    // the sorted pairs are read: their memory takes the waves' partial counts
+    int* part = reinterpret_cast<int*>(dyn);                            // (at least 16 ints: the launch asks for 128 bytes or more)
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) total += part[w];
+        row_count[row] = total;
+    }
+}
+
+// row_start[q] = sum of row_count[0 .. q - 1], row_start[Q] = count[0] = the total: ONE workgroup, thread t owns the rows
+// [t * per, (t + 1) * per); integers, so the result does not depend on how the sum is bracketed
+__global__ __launch_bounds__(1024) void undecided_scan_kernel(const int* __restrict__ row_count, int64_t Q, int64_t* __restrict__ row_start,
+                                                              int64_t* __restrict__ count) {
+    __shared__ int64_t part[1024];
+    const int64_t per = (Q + 1023) / 1024;
+    const int64_t r0 = min((int64_t)threadIdx.x * per, Q), r1 = min(r0 + per, Q);
+    int64_t sum = 0;
+    for (int64_t r = r0; r < r1; ++r) sum += row_count[r];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                                // inclusive scan of the 1024 partial sums
+        const int64_t add = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    int64_t run = part[threadIdx.x] - sum;
+    for (int64_t r = r0; r < r1; ++r) { row_start[r] = run; run += row_count[r]; }
+    if (threadIdx.x == 1023) { row_start[Q] = part[1023]; count[0] = part[1023]; }
+}
+
+// pos[row_start[row] + (number of flagged columns below k)] = row * K + k for every flagged column k: ascending within the row, rows in
+// order.  One workgroup of 256 per row; thread t owns the columns [t * per, (t + 1) * per), per <= 32.
+__global__ __launch_bounds__(256) void undecided_emit_kernel(const unsigned char* __restrict__ flags, const int* __restrict__ row_count,
+                                                             const int64_t* __restrict__ row_start, int K, int64_t* __restrict__ pos) {
+    __shared__ int part[256];
+    const int64_t row = blockIdx.x;
+    if (row_count[row] == 0) return;                                   // uniform over the workgroup
+    const unsigned char* f = flags + row * K;
+    const int per = (K + 255) / 256;
+    const int c0 = min((int)threadIdx.x * per, K), c1 = min(c0 + per, K);
+    int sum = 0;
+    for (int c = c0; c < c1; ++c) sum += f[c];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const int add = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += add;
+        __syncthreads();
+    }
+    int64_t at = row_start[row] + (part[threadIdx.x] - sum);            // < row_start[row] + row_count[row] <= Q * K: inside pos
+    for (int c = c0; c < c1; ++c)
+        if (f[c]) pos[at++] = row * K + c;
+}
+
+// values[pos[i]] <- referee[i], i < n, and what the overwritten values say about the bound: stats_max[0] = max |old - referee| (a difference
+// that is not a number does not enter the maximum), stats_bad[0] = how many i fail |old - referee| <= margin (a NaN difference fails).
+// ONE workgroup: a maximum and an integer count, reduced in a fixed order.  A position outside [0, Q * K) is skipped and counted as failing.
+__global__ __launch_bounds__(1024) void refine_apply_kernel(float* __restrict__ values, int64_t ld, int K, int64_t total,
+                                                            const int64_t* __restrict__ pos, const float* __restrict__ referee, int64_t n,
+                                                            float margin, float* __restrict__ stats_max, int64_t* __restrict__ stats_bad) {
+    __shared__ float wmax[16];
+    __shared__ int64_t wbad[16];
+    float m = 0.f;
+    int64_t bad = 0;
+    for (int64_t i = threadIdx.x; i < n; i += 1024) {
+        const int64_t at = pos[i];
+        if (at < 0 || at >= total) { bad += 1; continue; }
+        float* dst = values + (at / K) * ld + (at % K);
+        const float d = fabsf(*dst - referee[i]);
+        *dst = referee[i];
+        if (d > m) m = d;
+        if (!(d <= margin)) bad += 1;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        m = fmaxf(m, __shfl_xor(m, o, 64));
+        bad += __shfl_xor(bad, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) { wmax[threadIdx.x >> 6] = m; wbad[threadIdx.x >> 6] = bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tm = 0.f;
+        int64_t tb = 0;
+        for (int w = 0; w < 16; ++w) { tm = fmaxf(tm, wmax[w]); tb += wbad[w]; }
+        stats_max[0] = tm;
+        stats_bad[0] = tb;
+    }
+}
+
+// workspace of cir_rank_undecided: flags (Q * K bytes), row_count (Q int32), row_start (Q + 1 int64), each part on an 8-byte boundary
+struct UndecidedPlan { int64_t off_count, off_start, bytes; };
+
+static int undecided_plan(int64_t Q, int64_t K, UndecidedPlan* plan) {
+    if (Q <= 0 || K <= 0) return CIR_EINVAL;
+    if (K > RANK_SEG || Q > 0x7fffffffLL) return CIR_ESHAPE;
+    plan->off_count = (Q * K + 7) & ~(int64_t)7;
+    plan->off_start = plan->off_count + ((Q * 4 + 7) & ~(int64_t)7);
+    plan->bytes = plan->off_start + (Q + 1) * 8;
+    return CIR_OK;
+}
+
 struct RankPlan { int segs, group; int64_t bytes_a, bytes_b; };
 
 // the extents' checks and the workspace layout shared by the three entry points: list buffer A (Q * segs lists of k pairs, level 1's
@@ -239,6 +386,46 @@ extern "C" int cir_topk_select(const float* values, int64_t ld, const int64_t* e
         RankPair* t = in; in = out; out = t;
         lists = lists_out;
     }
+    CIR_LAUNCH_RESULT();
+}
+
+extern "C" int64_t cir_rank_undecided_workspace(int Q, int K) {
+    cir::UndecidedPlan plan;
+    const int code = cir::undecided_plan(Q, K, &plan);
+    return code != CIR_OK ? (int64_t)code : plan.bytes;
+}
+
+extern "C" int cir_rank_undecided(const float* values, int64_t ld, const unsigned char* active, float margin, int64_t* pos, int64_t* count,
+                                  int Q, int K, void* workspace, int64_t workspace_bytes, void* stream) {
+    using namespace cir;
+    CIR_CHECK_PTR(values); CIR_CHECK_PTR(pos); CIR_CHECK_PTR(count);
+    if (ld < K || !(margin >= 0.f) || !(margin <= 3.402823466e38f)) return CIR_EINVAL;      // (a NaN margin fails both comparisons)
+    UndecidedPlan plan;
+    const int code = undecided_plan(Q, K, &plan);
+    if (code != CIR_OK) return code;
+    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) != 0 || workspace_bytes < plan.bytes) return CIR_EINVAL;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    unsigned char* flags = reinterpret_cast<unsigned char*>(workspace);
+    int* row_count = reinterpret_cast<int*>(flags + plan.off_count);
+    int64_t* row_start = reinterpret_cast<int64_t*>(flags + plan.off_start);
+    const int pow2 = rank_pow2(K);
+    const size_t lds = (size_t)pow2 * sizeof(RankPair) < 128 ? 128 : (size_t)pow2 * sizeof(RankPair);
+    hipLaunchKernelGGL(undecided_flag_kernel, dim3((unsigned)Q), dim3(pow2 >= 2048 ? 1024 : 256), lds, s, values, ld, active, 2.f * margin, K, flags,
+                       row_count);
+    hipLaunchKernelGGL(undecided_scan_kernel, dim3(1), dim3(1024), 0, s, row_count, (int64_t)Q, row_start, count);
+    hipLaunchKernelGGL(undecided_emit_kernel, dim3((unsigned)Q), dim3(256), 0, s, flags, row_count, row_start, K, pos);
+    CIR_LAUNCH_RESULT();
+}
+
+extern "C" int cir_rank_refine_apply(float* values, int64_t ld, const int64_t* pos, const float* referee, int64_t n, float margin, void* stats,
+                                     int Q, int K, void* stream) {
+    CIR_CHECK_PTR(values); CIR_CHECK_PTR(stats);
+    if (n < 0 || Q <= 0 || K <= 0 || ld < K || !(margin >= 0.f) || !(margin <= 3.402823466e38f)) return CIR_EINVAL;
+    if (n > 0 && (pos == nullptr || referee == nullptr)) return CIR_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(stats) & 7u) != 0) return CIR_EALIGN;
+    if (n > (int64_t)Q * K) return CIR_ESHAPE;
+    hipLaunchKernelGGL(cir::refine_apply_kernel, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), values, ld, K, (int64_t)Q * K, pos,
+                       referee, n, margin, reinterpret_cast<float*>(stats), reinterpret_cast<int64_t*>(reinterpret_cast<char*>(stats) + 8));
     CIR_LAUNCH_RESULT();
 }
 

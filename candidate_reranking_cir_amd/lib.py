@@ -67,6 +67,10 @@ SIGNATURES = {
     "cir_topk_select_workspace": (c_int64, [c_int, c_int, c_int]),
     "cir_topk_select": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "cir_rank_of": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # rank refinement: the entries a fast mode cannot order, and the write-back of their exact scores (csrc/rank.hip)
+    "cir_rank_undecided_workspace": (c_int64, [c_int, c_int]),
+    "cir_rank_undecided": (c_int, [c_void_p, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "cir_rank_refine_apply": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int, c_int, c_void_p]),
     "cir_linear_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "cir_l2_normalize": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     # training-mode operators

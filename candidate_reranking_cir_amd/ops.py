@@ -658,6 +658,59 @@ def rank_of(values: torch.Tensor, cols: torch.Tensor, exclude: Optional[torch.Te
     return rank
 
 
+def _refine_rows(logits: torch.Tensor):
+    """The fp32 (Q, K) operand of cir_rank_undecided / cir_rank_refine_apply: a matrix, or a `[:, :K]` view of a wider one, with unit-stride
+    rows at least K apart.  Never copied: cir_rank_refine_apply writes into it."""
+    _need_cuda(logits)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise _lib.CirrankError("rank refinement needs an fp32 (Q, K) matrix with unit-stride rows at least K elements apart")
+    return logits.shape
+
+
+def rank_undecided(logits: torch.Tensor, margin: float, active: Optional[torch.Tensor] = None):
+    """Which entries of the fast logits (Q, K <= 8192) the fast mode cannot order (cir_rank_undecided): an entry within 2 * margin (fp32) of a
+    neighbour of its row sorted in argsort_desc's order.  `active` (Q,) uint8 / bool: a row whose byte is 0 yields nothing.  -> (pos, count):
+    pos int64 (Q * K,), whose first count[0] elements are the flat positions q * K + k in ascending order (the rest is not written); count
+    int64 (1,), on the device - reading it is the caller's one host read."""
+    q, k = _refine_rows(logits)
+    _need_cuda(active)
+    if active is not None:
+        active = (active.view(torch.uint8) if active.dtype == torch.bool else active).contiguous()
+        assert active.dtype == torch.uint8 and active.shape == (q,)
+    c = _lib.load()
+    need = c.cir_rank_undecided_workspace(q, k)
+    if need < 0:
+        _lib.check(int(need), "cir_rank_undecided_workspace")
+    work = torch.empty(need, dtype=torch.uint8, device=logits.device)
+    pos = torch.empty(q * k, dtype=torch.int64, device=logits.device)
+    count = torch.empty(1, dtype=torch.int64, device=logits.device)
+    code = c.cir_rank_undecided(logits.data_ptr(), logits.stride(0), _ptr(active), float(margin), pos.data_ptr(), count.data_ptr(), q, k,
+                                work.data_ptr(), need, _stream())
+    _lib.check(code, "cir_rank_undecided")
+    return pos, count
+
+
+def rank_refine_apply(logits: torch.Tensor, pos: torch.Tensor, referee_values: torch.Tensor, margin: float) -> torch.Tensor:
+    """logits.view(-1)[pos[i]] = referee_values[i] in place (positions q * K + k as rank_undecided gives them), with the run-time check of the
+    margin on exactly these entries (cir_rank_refine_apply).  -> stats, 16 bytes on the device (uint8): fp32 max |old - referee| at byte 0,
+    int64 number of entries with |old - referee| > margin at byte 8 (`refine_stats` reads both)."""
+    q, k = _refine_rows(logits)
+    _need_cuda(pos, referee_values)
+    assert pos.dtype == torch.int64 and pos.dim() == 1 and pos.is_contiguous()
+    assert referee_values.dtype == torch.float32 and referee_values.is_contiguous() and referee_values.shape == pos.shape
+    stats = torch.empty(2, dtype=torch.int64, device=logits.device)
+    code = _lib.load().cir_rank_refine_apply(logits.data_ptr(), logits.stride(0), pos.data_ptr(), referee_values.data_ptr(), pos.numel(),
+                                             float(margin), stats.data_ptr(), q, k, _stream())
+    _lib.check(code, "cir_rank_refine_apply")
+    return stats.view(torch.uint8)
+
+
+def refine_stats(stats: torch.Tensor):
+    """(max_deviation, violations) of a `rank_refine_apply` result: one copy to the host."""
+    raw = stats.cpu()
+    return float(raw[:4].view(torch.float32)[0]), int(raw[8:].view(torch.int64)[0])
+
+
 def gather_rows(src: torch.Tensor, index: Optional[torch.Tensor], dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """dst[i] = src[index[i]] converted to `dtype`; rows are src.shape[1:] flattened (index None = plain convert)."""
     _need_cuda(src, index)

@@ -116,10 +116,24 @@ def _check_bank_rows(ds: RelativeValSet, n_index: int):
 
 @torch.no_grad()
 def generate_val_predictions(blip_model, model_stage1, ds: RelativeValSet, index_features: torch.Tensor,
-                             query_batch: int = 8, rows: Optional[Sequence[int]] = None, kv_bank: Optional[list] = None):
+                             query_batch: int = 8, rows: Optional[Sequence[int]] = None, kv_bank: Optional[list] = None, *,
+                             refine_margin: Optional[float] = None, referee_index_features: Optional[torch.Tensor] = None,
+                             referee=None, on_violation: str = "warn", refine_stats: Optional[dict] = None):
     """Logits (len(rows), K) [and (len(rows), 5) subset logits when `ds.group_index` is set].
     `rows` selects a shard of the queries (default: all).  `kv_bank` (blip_model.build_kv_bank(index_features))
-    re-uses the per-image cross-attention K/V across all queries instead of re-projecting every candidate."""
+    re-uses the per-image cross-attention K/V across all queries instead of re-projecting every candidate.
+    `refine_margin` (opt-in; None = this function as it always was): the logits then go through `refine_predictions` with the exact-mode
+    bank `referee_index_features` (and `referee`, `on_violation` as there); `refine_stats`, a dict, receives its statistics."""
+    if refine_margin is not None:
+        if referee_index_features is None:
+            raise ValueError("refine_margin needs referee_index_features: extract_index_features on the referee model (the exact-mode fp32 bank)")
+        out = generate_val_predictions(blip_model, model_stage1, ds, index_features, query_batch, rows, kv_bank)
+        logits, glogits = out if ds.group_index is not None else (out, None)
+        logits, glogits, stats = refine_predictions(blip_model, model_stage1, ds, logits, glogits, referee_index_features, refine_margin,
+                                                    referee=referee, query_batch=query_batch, rows=rows, on_violation=on_violation)
+        if refine_stats is not None:
+            refine_stats.update(stats)
+        return (logits, glogits) if glogits is not None else logits
     dev = blip_model.device
     rows = list(range(len(ds))) if rows is None else list(rows)
     _check_bank_rows(ds, index_features.shape[0] if kv_bank is None else kv_bank[0].shape[0])
@@ -162,6 +176,130 @@ def generate_val_predictions(blip_model, model_stage1, ds: RelativeValSet, index
                                  "model.set_stream_dtype(torch.float32) on both models; in 'text32' (fp32 stream already) an fp16 operand term of "
                                  "the text side: call model.set_precision('exact') on both models (DESIGN.md section 2)")
     return (logits, glogits) if glogits is not None else logits
+
+
+# ------------------------------------------------------------------------------------------------ rank refinement
+class RefineBoundError(FloatingPointError):
+    """`refine_predictions(on_violation="raise")`: a re-scored entry lay further than `margin` from its fast logit."""
+
+
+def _referee_pair(blip_model, model_stage1, referee):
+    if referee is None:
+        return blip_model.referee(), model_stage1.referee()
+    blip_ref, stage1_ref = referee
+    if blip_ref.precision != "exact" or stage1_ref.precision != "exact":
+        raise ValueError("referee = (stage-II model, stage-I model), both in the 'exact' precision (model.referee())")
+    return blip_ref, stage1_ref
+
+
+@torch.no_grad()
+def refine_predictions(blip_model, model_stage1, ds: RelativeValSet, logits: torch.Tensor, glogits: Optional[torch.Tensor],
+                       referee_index_features: torch.Tensor, margin: float, *, referee=None, query_batch: int = 8,
+                       rows: Optional[Sequence[int]] = None, on_violation: str = "warn"):
+    """Phase 2 of a fast-mode run: the exact mode scores again only the entries whose order the fast logits cannot decide, and overwrites
+    them IN PLACE.  `logits` (len(rows), K) and `glogits` (len(rows), 5) or None are `generate_val_predictions`' outputs for the same `ds`
+    and `rows`, from models in any fast precision.
+
+    The rule (include/cirrank.h, cir_rank_undecided): in every row sorted as `argsort_desc` sorts it, neighbours whose fp32 difference is at
+    most 2 * margin are linked; an entry linked to a neighbour is undecided.  If |fast - exact| <= margin on every entry of a row, the
+    stable descending argsort of the refined row equals that of the exact mode's full row at every position - so metrics and submission
+    code, which only sort the matrix (validate_stage2.py:53, 174, 188), give the exact mode's results.  The guarantee is conditional on the
+    margin (`calibrate_margin`); `stats` reports at run time whether it held on the entries that were re-scored.
+
+    `referee_index_features`: the exact-mode bank, `extract_index_features(images, referee_model)` (fp32); the caller builds it once.
+    `referee`: (stage-II referee, stage-I referee) as `model.referee()` returns them; None builds the pair here - and only when at least one
+    entry is undecided (margin 0 on rows without ties packs and launches nothing).  Pass the pair to keep its packed engines across calls.
+    Skipped queries (no positive in the top-K) hold SKIP_FILL everywhere and are left alone.  Host traffic: the two counts are read, then the
+    undecided positions are copied once to group them by query and by caption length like phase 1; z_t is formed once per affected query.
+
+    -> (logits, glogits, stats); stats: `entries` (of all scored rows), `rescored`, `queries_rescored`, `max_deviation` (max |fast - exact|
+    over the re-scored entries), `violations` (how many of them exceed `margin`) and `margin`.  violations > 0 means the bound was wrong
+    for this data and the order is NOT certified: one warning (`on_violation="warn"`) or `RefineBoundError` ("raise"; the matrices are
+    already overwritten then)."""
+    margin = float(margin)
+    if not (0.0 <= margin < float("inf")):
+        raise ValueError(f"refine_predictions: margin {margin} (finite and >= 0)")
+    if on_violation not in ("warn", "raise"):
+        raise ValueError('on_violation is "warn" or "raise"')
+    dev = logits.device
+    rows = list(range(len(ds))) if rows is None else list(rows)
+    if logits.shape != (len(rows), ds.K) or (glogits is not None and (ds.group_index is None or glogits.shape != (len(rows), ds.group_index.shape[1]))):
+        raise ValueError("refine_predictions: logits / glogits are not generate_val_predictions' outputs for this dataset and `rows`")
+    if referee_index_features.dtype != torch.float32:
+        raise ValueError("referee_index_features is the exact-mode bank: extract_index_features on the referee (fp32)")
+    has_pos = np.asarray(ds.labels.any(axis=1))[rows]
+    mats = [(logits, torch.as_tensor(has_pos.astype(np.uint8), device=dev), ds.cand_index)]
+    entries = int(has_pos.sum()) * ds.K
+    if glogits is not None:
+        mats.append((glogits, None, ds.group_index))                     # every query's subset is scored (validate_stage2.py:261-269)
+        entries += glogits.numel()
+    found = [ops.rank_undecided(m, margin, act) for m, act, _ in mats]
+    counts = [int(c) for _, c in found]                                  # the host reads: one count per matrix
+    stats = dict(entries=entries, rescored=sum(counts), queries_rescored=0, max_deviation=0.0, violations=0, margin=margin)
+    if sum(counts) == 0:
+        return logits, glogits, stats
+    _check_bank_rows(ds, referee_index_features.shape[0])
+    blip_ref, stage1_ref = _referee_pair(blip_model, model_stage1, referee)
+    # the undecided (query, candidate) pairs, grouped by query: per[q] = [(matrix, place in that matrix's pos, bank row), ...]
+    per = {}
+    for which, ((m, _, names), (pos, _), n) in enumerate(zip(mats, found, counts)):
+        flat = pos[:n].cpu().numpy()
+        width = m.shape[1]
+        for i, (r, c) in enumerate(zip((flat // width).tolist(), (flat % width).tolist())):
+            q = rows[r]
+            per.setdefault(q, []).append((which, i, int(names[q][c])))
+    stats["queries_rescored"] = len(per)
+    outs, src, base = [], [np.empty(n, dtype=np.int64) for n in counts], 0
+    for length, bucket in sorted(_length_buckets(ds, blip_ref.tokenizer, sorted(per)).items()):
+        for s in range(0, len(bucket), query_batch):
+            qs = bucket[s:s + query_batch]
+            ids, mask = _tokenise(ds, blip_ref.tokenizer, qs, length, dev)
+            ref = ops.gather_rows(referee_index_features, torch.as_tensor(ds.ref_index[qs], device=dev))
+            z = stage1_ref.z_t(ref, ids, mask)                             # once per affected query
+            bank_rows, qidx = [], []
+            for j, q in enumerate(qs):
+                for which, i, bank_row in per[q]:
+                    src[which][i] = base + len(bank_rows)
+                    bank_rows.append(bank_row); qidx.append(j)
+            outs.append(blip_ref.score(z.last_hidden_state, ids, mask, ops.gather_rows(referee_index_features, torch.as_tensor(bank_rows, device=dev)),
+                                       torch.as_tensor(qidx, device=dev)))
+            base += len(bank_rows)
+    scores = torch.cat(outs)
+    applied = []
+    for (m, _, _), (pos, _), n, order in zip(mats, found, counts, src):
+        if n:
+            applied.append(ops.rank_refine_apply(m, pos[:n], scores[torch.as_tensor(order, device=dev)].contiguous(), margin))
+    for dev_stats in applied:
+        worst, bad = ops.refine_stats(dev_stats)
+        stats["max_deviation"] = max(stats["max_deviation"], worst)
+        stats["violations"] += bad
+    if stats["violations"]:
+        msg = (f"rank refinement: {stats['violations']} of {stats['rescored']} re-scored entries lie further than the margin {margin:g} from "
+               f"their fast logits (max {stats['max_deviation']:g}): the bound does not hold for this data and the order is not certified")
+        if on_violation == "raise":
+            raise RefineBoundError(msg)
+        import warnings
+        warnings.warn(msg, RuntimeWarning, stacklevel=2)
+    return logits, glogits, stats
+
+
+@torch.no_grad()
+def calibrate_margin(blip_model, model_stage1, ds: RelativeValSet, index_features: torch.Tensor, referee_index_features: torch.Tensor, *,
+                     rows: Optional[Sequence[int]] = None, referee=None, query_batch: int = 8, safety: float = 2.0):
+    """A margin for `refine_predictions` from a sample of queries (`rows`): the sample is scored in full by the fast models and by the
+    referee pair, -> (safety * max |fast - exact|, that raw maximum) over every scored entry (subset logits included).  `safety` is the
+    caller's choice: the maximum over a sample is a lower bound of the maximum over the split, and refinement's guarantee is conditional
+    on the margin - its `stats` report whether it held where it mattered."""
+    if not safety >= 1.0:
+        raise ValueError("calibrate_margin: safety >= 1")
+    rows = list(range(len(ds))) if rows is None else list(rows)
+    blip_ref, stage1_ref = _referee_pair(blip_model, model_stage1, referee)
+    fast = generate_val_predictions(blip_model, model_stage1, ds, index_features, query_batch, rows)
+    exact = generate_val_predictions(blip_ref, stage1_ref, ds, referee_index_features, query_batch, rows)
+    raw = 0.0
+    for f, e in zip(fast, exact) if ds.group_index is not None else ((fast, exact),):
+        raw = max(raw, float((f.double() - e.double()).abs().max()))        # (skipped rows hold the fill value on both sides: 0)
+    return float(np.nextafter(np.float32(safety * raw), np.float32(np.inf))) if raw > 0.0 else 0.0, raw
 
 
 # ------------------------------------------------------------------------------------------------ reference signatures

@@ -385,6 +385,36 @@ int cir_topk_select(const float* values, int64_t ld, const int64_t* exclude, int
 int cir_rank_of(const float* values, int64_t ld, const int64_t* cols, const int64_t* exclude, int64_t* rank, int Q, int n, int m, void* stream);
 
 /*
+ * Rank refinement (csrc/rank.hip; three entry points, additive within ABI v15 like cir_topk_select): a fast precision mode's logits decide the
+ * order of a row wherever two values are far enough apart; only the rest is scored again by the exact mode.  Consumers of a logits matrix only
+ * ever sort its rows (validate_stage2.py:53, 174, 188), so the matrix with the undecided entries overwritten sorts as the exact mode's.
+ * The rule, for a row s and a margin >= 0, width = 2 * margin (exact in fp32): sort the row in cir_topk_desc's order (value descending, ties to
+ * the lower column, a NaN as -inf); neighbours a, b of the sorted row are linked iff the fp32 difference a - b <= width (a difference that is
+ * not a number links nothing); an entry is undecided iff it is linked to a neighbour.  If |fast - exact| <= margin on every entry of the row,
+ * the stable descending argsort of the refined row equals that of the exact row at every position.
+ *
+ * cir_rank_undecided (validate_stage2.py:53, 174, 188): values fp32 (Q, K), rows ld >= K elements apart, never written; active uint8 (Q) or
+ *   NULL: a row whose byte is 0 yields nothing (a skipped query holds one fill value everywhere); margin finite and >= 0 (CIR_EINVAL otherwise).
+ *   pos int64 (capacity Q * K) receives the flat positions q * K + k of all undecided entries in ascending order, count int64 (1) their number;
+ *   pos beyond count is not written.  1 <= K <= 8192 (one row per workgroup in LDS, like cir_topk_desc; CIR_ESHAPE beyond).  Three launches: a
+ *   sort and flag pass per row, one workgroup that adds up the rows' counts, a compaction pass per row.  No atomics; no workgroup waits for
+ *   another; every count is an integer: the same input gives the same pos and count bit for bit.
+ *   workspace: a caller-owned device buffer of at least cir_rank_undecided_workspace(Q, K) bytes, 8-byte aligned (CIR_EINVAL when NULL,
+ *   misaligned or smaller); its contents are scratch.
+ * cir_rank_undecided_workspace (validate_stage2.py:53, 174, 188): pure host function; the bytes cir_rank_undecided needs for these extents, or a
+ *   negative CIR_E* code for extents it refuses.
+ * cir_rank_refine_apply (validate_stage2.py:53, 174, 188): values[q * ld + k] <- referee[i] for pos[i] = q * K + k, i < n (n = 0: nothing is
+ *   written but stats).  stats: 16 bytes on the device, 8-byte aligned: fp32 max_i |old - referee| at byte 0 (a difference that is not a number
+ *   does not enter the maximum), int64 at byte 8 the number of i that fail |old - referee| <= margin - the run-time check of the bound on
+ *   exactly the entries it matters for.  A position outside [0, Q * K) is not written and counts as failing.  One workgroup, fixed-order reduction.
+ */
+int64_t cir_rank_undecided_workspace(int Q, int K);
+int cir_rank_undecided(const float* values, int64_t ld, const unsigned char* active, float margin, int64_t* pos, int64_t* count, int Q, int K,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int cir_rank_refine_apply(float* values, int64_t ld, const int64_t* pos, const float* referee, int64_t n, float margin, void* stats, int Q, int K,
+                          void* stream);
+
+/*
  * fp32 y (M,N) = x (M,K) W(N,K)^T + bias (mode 0), 1 - x W^T (mode 1) or x W^T - 1 (mode 2, the exact
  * negative of mode 1, so that cir_topk_desc ranks by ascending distance): stage I's 256-d heads
  * vision_proj / text_proj (blip_stage1.py:42-43, 58, 83) and its distance matrix
