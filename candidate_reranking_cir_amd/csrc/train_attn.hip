@@ -37,6 +37,14 @@ struct TAttnArgs {
     uint64_t seed;
 };
 
+// A group whose EVERY key lies under a saturated mask (finfo.min: clamped to kMaskClamp): in fp32 every score of such a row IS the clamp
+// (q.k is absorbed), the forward's rows are uniform over the Lk keys, and its lse = m + log2 l is the clamp again - log2 l is absorbed as
+// well, so exp2(s + mask - lse) cannot rebuild P = 1 / Lk (dQ was NaN, dK / dV Lk times too large).  The backward kernels recognise the
+// group by that lse - no other row can have it - and rebuild what the forward used: score scale 0, mask weight 0, -lse = -log2 Lk.  The mask
+// is the group's, so the condition is uniform over a wave; it costs nothing per element.
+constexpr float kMaskClamp = -2.0e38f;
+constexpr float kSatLse = kMaskClamp * kLog2e;                  // = fmaf(kMaskClamp, kLog2e, s) for every |s| < 1e30
+
 // gradient store of a transposed accumulator (same element map) at element offset `off` of `base`: fp32 or the operand type
 template <typename T>
 __device__ __forceinline__ void store_grad(const f32x16 (&acc)[2], void* base, int64_t off, int grad16, float mul) {
@@ -105,7 +113,7 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const TAttnArgs a) {
         for (int i = 0; i < 16; ++i) {
             const int key = key0 + acc_row(i, hh);
             float x = s[i] * sl;
-            if constexpr (MASKED) x = fmaf(fmaxf(mp[min(key, a.Lk - 1)], -2.0e38f), kLog2e, x);
+            if constexpr (MASKED) x = fmaf(fmaxf(mp[min(key, a.Lk - 1)], kMaskClamp), kLog2e, x);
             sv[i] = key < a.Lk ? x : -INFINITY;
             mx = fmaxf(mx, sv[i]);
         }
@@ -150,6 +158,21 @@ __global__ __launch_bounds__(256) void tattn_fwd_kernel(const TAttnArgs a) {
 // chain is kept minimal: x = s * sl + c with c = mask - LSE prepared per row / column (-inf for rows or keys past the extents: p = 0, no
 // `valid` selects), the softmax scale is applied ONCE to the dQ / dK accumulators at the store instead of to every dS element, and
 // dS / scale = Pd16 * dPd - P_f * D needs one multiply and one fma.
+// The packed 16-bit operand of a matrix product as an OPAQUE value: whatever else is formed from its elements afterwards (the fp32 row sum of
+// the same 16-bit numbers) is formed from the operand's own bits.  Left to itself the compiler selects the fp32 -> fp16 conversion once per
+// consumer: v_fma_mixlo_f16 - the product that formed the value and the conversion in ONE rounding - for the copy that is widened again,
+// v_mul_f32 + v_cvt_pk_f16_f32 - two roundings - for the copy packed into the operand, and the two differ by an fp16 ulp about once in 2^13
+// elements: the residue sum_j dS16_j of the dQ kernel then no longer belongs to the dS16 the product consumed (tests/test_attn_bwd_gpu.py:
+// dQ[:, 1], where every key is 1, off by one ulp of dS times the scale).  The empty asm costs no instruction.  (bf16 has no such fused form.)
+template <typename V>
+__device__ __forceinline__ void opaque128(V& v) {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u4;
+    static_assert(sizeof(V) == sizeof(u4), "one 128-bit operand");
+    u4 b = __builtin_bit_cast(u4, v);
+    asm("" : "+v"(b));
+    v = __builtin_bit_cast(V, b);
+}
+
 struct Adj { float pd, ds; };
 template <typename T, bool DROP>
 __device__ __forceinline__ Adj adjoint(float s, float dp, float sl, float c, float dsum, float keep, float ikeep, bool kept) {
@@ -217,11 +240,14 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dq_kernel(const TAttnArgs a)
         if (hh == 0 && q0 + r < a.Lq) a.dsum[gh * a.Lq + q0 + r] = dsum;
     }
     const bool qvalid = q0 + r < a.Lq;
-    const float nlse = qvalid ? -a.lse[gh * a.Lq + qrow] : -INFINITY;     // a query row past Lq: p = 0 everywhere
+    const float lse_r = a.lse[gh * a.Lq + qrow];
+    const bool gsat = MASKED && lse_r == kSatLse;                  // every key of the group saturated (above): the same for every row
+    const float nlse = qvalid ? (gsat ? -log2f((float)a.Lk) : -lse_r) : -INFINITY;     // a query row past Lq: p = 0 everywhere
+    const float l2e = gsat ? 0.f : kLog2e;
     char* kl = smem + wave * 4096;
     int voff[2];
     tr_offsets(lane, voff);
-    const float sl = a.scale * kLog2e;
+    const float sl = gsat ? 0.f : a.scale * kLog2e;
     const float keep = a.p_drop > 0.f ? 1.0f / (1.0f - a.p_drop) : 1.0f, ikeep = 1.0f - a.p_drop;
     const uint32_t rkey = drop_row_key(a.seed, (uint64_t)(gh * a.Lq + qrow)), thr = drop_threshold(a.p_drop);
 
@@ -259,19 +285,20 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dq_kernel(const TAttnArgs a)
                 const int key = key0 + acc_row(i, hh);
                 float c = nlse;
                 if constexpr (decltype(edge_c)::value) {
-                    if constexpr (MASKED) c = fmaf(fmaxf(mp[min(key, a.Lk - 1)], -2.0e38f), kLog2e, nlse);
+                    if constexpr (MASKED) c = fmaf(fmaxf(mp[min(key, a.Lk - 1)], kMaskClamp), l2e, nlse);
                     c = key < a.Lk ? c : -INFINITY;
                 }
                 if (DROP && (i & 1) == 0) bits = drop_bits(rkey, key);
                 const Adj ad = adjoint<T, DROP>(s[i], dp[i], sl, c, dsum, keep, ikeep, DROP ? kept16(bits, (i & 1) * 16, thr) : true);
-                const T ds16 = static_cast<T>(ad.ds);
-                dsf[i >> 3][i & 7] = ds16;
+                dsf[i >> 3][i & 7] = static_cast<T>(ad.ds);
                 pdf[i >> 3][i & 7] = static_cast<T>(ad.pd);        // (exact: pd is a 16-bit value)
-                esum += static_cast<float>(ds16);
                 psum += ad.pd;
             }
         };
         if (edge) elements(std::true_type{}); else elements(std::false_type{});
+        if constexpr (std::is_same<T, _Float16>::value) { opaque128(dsf[0]); opaque128(dsf[1]); }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) esum += static_cast<float>(dsf[i >> 3][i & 7]);      // the operand's own elements (opaque128)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         tr_accumulate<T>(dq, kl, voff, dsf);                    // dQ^T[dh][q] += K^T[dh][key] (dS / scale)^T[key][q]
@@ -312,20 +339,22 @@ __global__ __launch_bounds__(256, 2) void tattn_bwd_dkv_kernel(const TAttnArgs a
     X8 kfb[4], vfb[4];                                          // this wave's 32 keys as B operands (columns)
     frag_load<T>(reinterpret_cast<const T*>(a.k) + g * a.k_sg + h * a.k_sh + (int64_t)krow * a.k_sr + 8 * hh, kfb);
     frag_load<T>(reinterpret_cast<const T*>(a.v) + g * a.v_sg + h * a.v_sh + (int64_t)krow * a.v_sr + 8 * hh, vfb);
+    const bool gsat = MASKED && a.lse[gh * a.Lq] == kSatLse;      // every key of the group saturated (above): any row of it tells
+    const float nlk = -log2f((float)a.Lk);
     float maskv = 0.f;
-    if constexpr (MASKED) maskv = fmaxf(a.mask[g * a.Lk + krow], -2.0e38f) * kLog2e;
+    if constexpr (MASKED) maskv = gsat ? 0.f : fmaxf(a.mask[g * a.Lk + krow], kMaskClamp) * kLog2e;
     char* ql = smem + wave * (2 * 4096 + 256);
     char* dl = ql + 4096;
     float* stat = reinterpret_cast<float*>(dl + 4096);          // [0, 32): -LSE of the tile's rows, [32, 64): their D
     int voff[2];
     tr_offsets(lane, voff);
-    const float sl = a.scale * kLog2e;
+    const float sl = gsat ? 0.f : a.scale * kLog2e;
     const float keep = a.p_drop > 0.f ? 1.0f / (1.0f - a.p_drop) : 1.0f, ikeep = 1.0f - a.p_drop;
     const float* stp = (hh == 0 ? a.lse : a.dsum) + gh * a.Lq;
     auto stat_load = [&](int q0) -> float {
         const int qi = q0 + r;
         const float v = stp[min(qi, a.Lq - 1)];
-        return hh == 0 ? (qi < a.Lq ? -v : -INFINITY) : v;      // a query row past Lq: p = 0
+        return hh == 0 ? (qi < a.Lq ? (gsat ? nlk : -v) : -INFINITY) : v;      // a query row past Lq: p = 0
     };
     const uint32_t thr = drop_threshold(a.p_drop);
     const uint32_t rkey0 = drop_row_key(a.seed, (uint64_t)(gh * a.Lq + 4 * hh));    // + (query - 4 hh) * kDropWeyl: the rows of a tile are a Weyl step apart

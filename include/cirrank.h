@@ -485,7 +485,10 @@ int cir_softmax_dropout_bwd(const void* P, int64_t ld_p, const float* dPd, int64
  * fused kernels, see below: row = (g * H + h) * Lq + query, col = key), so no score / probability tensor exists in memory.  Tensors are head views: element
  * (g, h, row, d) at base + g * x_sg + h * x_sh + row * x_sr + d; out and d_out share one layout; mask fp32 (G, Lk) additive or NULL;
  * dsum_scratch fp32 (G * H * Lq) receives rowsum(d_out * out) - with out taken from its optional fp32 twin out32 (written by the
- * forward, same layout): it then equals sum_j Pd_ij dPd_ij term for term and the row sums of dS vanish.  Replaces, for BertSelfAttention.forward in train() mode
+ * forward, same layout): it then equals sum_j Pd_ij dPd_ij term for term and the row sums of dS vanish.  Mask values are clamped at -2e38; a
+ * group whose EVERY key is at that clamp (finfo.min on all keys) has uniform rows and lse = -2e38 * log2(e) exactly, and the backward
+ * recognises it by that lse (its gradients are those of the uniform rows).  A row whose keys are all masked by huge values ABOVE the clamp
+ * (say -1e35 everywhere) is not supported: its lse absorbs log2 of the row sum and the backward cannot rebuild P.  Replaces, for BertSelfAttention.forward in train() mode
  * (nlvr_encoder.py:140-222, dropout :207) and its adjoint, the cir_bmm / cir_softmax_dropout[_bwd] chain. */
 int cir_attention_train_fwd(const void* q, int64_t q_sg, int64_t q_sh, int64_t q_sr, const void* k, int64_t k_sg, int64_t k_sh, int64_t k_sr,
                             const void* v, int64_t v_sg, int64_t v_sh, int64_t v_sr, const float* mask, void* out, int64_t o_sg, int64_t o_sh,

@@ -243,7 +243,8 @@ def core_terms(q, k, v, mask, dt, depth=64):
     b32 = SECOND * ((p * (eps + r)) @ v.abs() + out.abs() * pe + a * ((2 * lk + 4 * nkt + 7) * U))
     lse = torch.logsumexp(x * LN2, -1) * LOG2E
     b_lse = pe[..., 0] / LN2 + ((lk + 2) * U + 4 * U) / LN2 + 2 * U * (math.log2(lk) + 6) + 2 * U * lse.abs()
-    return dict(out=out, p=p, lse=lse, b32=b32, b_lse=b_lse, e=(p * (eps + r)).sum(-1), p_term=(p * r) @ v.abs())
+    return dict(out=out, p=p, lse=lse, b32=b32, b_lse=b_lse, e=(p * (eps + r)).sum(-1), p_term=(p * r) @ v.abs(),
+                eps=eps, r=r, x=x, sat=sat)                         # the elementwise pieces, for tests/attn_bwd_cases.py
 
 
 def _terms(c):
@@ -314,11 +315,13 @@ CORRECT = ("lazy", "plain", "lazy_ftz")
 WRONG = ("drop_last", "pad_key", "no_l_rescale", "vote_rows_only", "mask_shift", "alpha_after_move", "mask_unclamped", "p_unscaled_tail", "ge_no_move")
 
 
-def emulate_core(q, k, v, mask, dt, variant="lazy", stats=None):
+def emulate_core(q, k, v, mask, dt, variant="lazy", stats=None, w=None):
     """The kernels' online softmax in torch fp32: 32-key tiles, 32-row query tiles (rows past Lq repeat row Lq - 1 and VOTE, as in the
     kernels), the lazy vote with threshold 6 (`plain`: rescale on every tile), P rounded to `dt`, fp32 O and l.
     -> dict(out32 (N, Lq, Dv) fp32 before the output rounding, lse (N, Lq)); stats["late"] (N, nqt): rescales taken behind key tile 0.
     `lazy_ftz` is `lazy` with the fp16 subnormals of P flushed to zero: correct as well - the bound holds either way.
+    `w` (N, Lq, Lk): the dropout weights keep / (1 - p) of tattn_fwd_kernel - they multiply P at the running reference before its
+    rounding, in the numerator only (l sums the unweighted values); tests/attn_bwd_cases.py.
     Wrong variants (each wrong in value only):
       drop_last         the last valid key (Lk - 1) never enters
       pad_key           a ragged last tile lets ONE zero-filled key past Lk in (score 0, value 0)
@@ -352,6 +355,8 @@ def emulate_core(q, k, v, mask, dt, variant="lazy", stats=None):
     o = torch.zeros((n, rows, v.shape[2]))
     late = torch.zeros((n, nqt), dtype=torch.int64)
     vf = v.float()
+    if w is not None:
+        wf = torch.cat([w.float(), w.float()[:, -1:].expand(n, pad, -1)], 1) if pad else w.float()
     for t0 in range(0, lk, 32):
         t1 = min(t0 + 32, lk)
         sv = s_all[:, :, t0:t1] * sl
@@ -389,6 +394,8 @@ def emulate_core(q, k, v, mask, dt, variant="lazy", stats=None):
         m = m_moved
         p = torch.exp2(sv - m[:, :, None])
         l = l * a_l + p.sum(-1)
+        if w is not None:
+            p = p * wf[:, :, t0:t1]
         p16 = p.to(dt).float() if dt != F32 else p
         if variant == "lazy_ftz" and dt == F16:
             p16 = torch.where(p16 < 2.0 ** -14, torch.zeros_like(p16), p16)
