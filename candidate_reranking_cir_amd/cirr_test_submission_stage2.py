@@ -48,12 +48,17 @@ def generate_cirr_test_predictions(blip_model, model_stage1, relative_test_datas
 
 @torch.no_grad()
 def _cirr_test_dicts(blip_model, model_stage1, ds: RelativeValSet, index_features: torch.Tensor, index_names: Sequence[str],
-                     pair_ids: Sequence[int], query_batch: int = 8, kv_bank=None) -> Tuple[Dict[str, List[str]], Dict[str, List[str]]]:
-    """The native form of `generate_cirr_test_dicts`."""
+                     pair_ids: Sequence[int], query_batch: int = 8, kv_bank=None, *, refine_margin=None, referee_index_features=None,
+                     referee=None, on_violation: str = "warn", refine_stats=None) -> Tuple[Dict[str, List[str]], Dict[str, List[str]]]:
+    """The native form of `generate_cirr_test_dicts`.  `refine_margin` (opt-in, with `referee_index_features` etc. as in
+    `generate_val_predictions`): rank refinement with first=50 - the 50 names written per pair are the first 50 places, so only clusters that
+    reach into them are scored again; the 3 subset names come from the subset matrix, refined by the full rule."""
     all_true = RelativeValSet(ref_index=ds.ref_index, cand_index=ds.cand_index, labels=np.ones_like(ds.cand_index, dtype=bool),
                               captions=ds.captions, input_ids=ds.input_ids, attention_mask=ds.attention_mask,
                               group_index=ds.group_index, target_index=ds.target_index)
-    logits, glogits = generate_val_predictions(blip_model, model_stage1, all_true, index_features, query_batch=query_batch, kv_bank=kv_bank)
+    refine = {} if refine_margin is None else dict(refine_margin=refine_margin, referee_index_features=referee_index_features, referee=referee,
+                                                   on_violation=on_violation, refine_stats=refine_stats, refine_first=50)
+    logits, glogits = generate_val_predictions(blip_model, model_stage1, all_true, index_features, query_batch=query_batch, kv_bank=kv_bank, **refine)
     names = np.asarray(index_names)
     order = ops.argsort_desc(logits).cpu().numpy()
     sorted_names = np.take_along_axis(names[ds.cand_index], order, axis=1)

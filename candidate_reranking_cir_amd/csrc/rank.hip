@@ -12,7 +12,8 @@
 //
 // Rank refinement (cir_rank_undecided, cir_rank_refine_apply; validate_stage2.py:53, 174, 188): the same sort and order, on rows of at most
 // 8192 logits of a fast precision mode - which entries lie within 2 * margin of a neighbour of the sorted row, so that only they are scored
-// again by the exact mode, and the write-back of those scores with a check of the margin on the values they replace.
+// again by the exact mode, and the write-back of those scores with a check of the margin on the values they replace.  cir_rank_undecided_cuts
+// keeps of them only the runs of linked places that reach into the first places or straddle a recall cut-off: what top-k lists and Recall@c read.
 #include "common.hpp"
 
 namespace cir {
@@ -238,6 +239,122 @@ __global__ __launch_bounds__(1024) void undecided_flag_kernel(const float* __res
     }
 }
 
+// ---- the same, for the first places and the recall cut-offs only (cir_rank_undecided_cuts) ----
+// bound[0 .. n): the boundaries B of {first} and the cuts with 1 <= B <= K - 1 (the host drops the others: they straddle nothing).
+struct UndecidedBounds { int first, n, bound[9]; };
+
+constexpr int CUTS_PER_THREAD = 8;                                      // places per thread: 8192 / 1024, or at most 1024 / 256
+constexpr int CUTS_LDS_INTS = 16 * 18 + 18 + 16;                        // the waves' partial L / R, the reduced L / R, the waves' partial counts
+
+// Same sort, same links.  A linked place j is flagged iff j < first, or L_B <= j <= R_B for a boundary B whose link (B - 1, B) holds, where
+// [L_B, R_B] is the cluster that straddles B: L_B the largest place <= B - 1 that is place 0 or has no link to its predecessor, R_B the
+// smallest place >= B that is place K - 1 or has no link to its successor.  A boundary whose link does not hold gets R_B = -1: nothing lies
+// in [L_B, -1].  Every thread keeps its places' columns and links in registers, so the memory of the sorted pairs (all 64 KiB at K = 8192)
+// can take the integer max / min reductions: waves by shuffles, the 16 waves in a fixed order.
+__global__ __launch_bounds__(1024) void undecided_cuts_flag_kernel(const float* __restrict__ values, int64_t ld, const unsigned char* __restrict__ active,
+                                                                   float width, int K, UndecidedBounds bounds, unsigned char* __restrict__ flags,
+                                                                   int* __restrict__ row_count) {
+    extern __shared__ __attribute__((aligned(16))) char dyn[];
+    RankPair* p = reinterpret_cast<RankPair*>(dyn);
+    const int64_t row = blockIdx.x;
+    unsigned char* f = flags + row * K;
+    if (active != nullptr && active[row] == 0) {                       // uniform over the workgroup: nobody reaches a barrier
+        for (int i = threadIdx.x; i < K; i += blockDim.x) f[i] = 0;
+        if (threadIdx.x == 0) row_count[row] = 0;
+        return;
+    }
+    int n_pow2 = 2;
+    while (n_pow2 < K) n_pow2 <<= 1;
+    const float* src = values + row * ld;
+    for (int i = threadIdx.x; i < n_pow2; i += blockDim.x) {
+        RankPair e;
+        if (i < K) { e.v = rank_key(src[i]); e.i = i; }
+        else { e.v = -INFINITY; e.i = RANK_PAD; }
+        p[i] = e;
+    }
+    __syncthreads();
+    rank_sort_first(p, n_pow2, n_pow2);
+    int col[CUTS_PER_THREAD];
+    unsigned prev_link = 0, next_link = 0;                              // bit i: place threadIdx.x + i * blockDim.x is linked to its predecessor / successor
+    int lo[9], hi[9];
+#pragma unroll
+    for (int b = 0; b < 9; ++b) { lo[b] = -1; hi[b] = K; }
+#pragma unroll
+    for (int i = 0; i < CUTS_PER_THREAD; ++i) {
+        const int j = threadIdx.x + i * blockDim.x;
+        col[i] = 0;
+        if (j < K) {
+            const RankPair e = p[j];
+            col[i] = e.i;
+            const bool lp = j > 0 && (p[j - 1].v - e.v) <= width;
+            const bool ln = j + 1 < K && (e.v - p[j + 1].v) <= width;
+            prev_link |= lp ? 1u << i : 0u;
+            next_link |= ln ? 1u << i : 0u;
+#pragma unroll
+            for (int b = 0; b < 9; ++b) {
+                if (b < bounds.n) {
+                    const int B = bounds.bound[b];
+                    if (j <= B - 1 && !lp) lo[b] = max(lo[b], j);
+                    if (j >= B && !ln) hi[b] = min(hi[b], j);
+                    if (j == B && !lp) hi[b] = -1;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < 9; ++b) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo[b] = max(lo[b], __shfl_xor(lo[b], o, 64));
+            hi[b] = min(hi[b], __shfl_xor(hi[b], o, 64));
+        }
+    }
+    __syncthreads();                                                    // the sorted pairs are read: their memory takes the reductions
+    int* part = reinterpret_cast<int*>(dyn);                            // (the launch asks for CUTS_LDS_INTS ints or more)
+    int* red = part + 16 * 18;
+    int* cnt = red + 18;
+    const int waves = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int b = 0; b < 9; ++b) { part[(threadIdx.x >> 6) * 18 + b] = lo[b]; part[(threadIdx.x >> 6) * 18 + 9 + b] = hi[b]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 18) {
+        const bool is_lo = threadIdx.x < 9;
+        int r = part[threadIdx.x];
+        for (int w = 1; w < waves; ++w) r = is_lo ? max(r, part[w * 18 + threadIdx.x]) : min(r, part[w * 18 + threadIdx.x]);
+        red[threadIdx.x] = r;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int b = 0; b < 9; ++b) {
+        if (b < bounds.n) { lo[b] = red[b]; hi[b] = red[9 + b]; }
+        else { lo[b] = 0; hi[b] = -1; }
+    }
+    int mine = 0;
+#pragma unroll
+    for (int i = 0; i < CUTS_PER_THREAD; ++i) {
+        const int j = threadIdx.x + i * blockDim.x;
+        if (j < K) {
+            bool sel = j < bounds.first;
+#pragma unroll
+            for (int b = 0; b < 9; ++b) sel = sel || (lo[b] <= j && j <= hi[b]);
+            const bool und = sel && (((prev_link | next_link) >> i) & 1u) != 0;
+            f[col[i]] = und ? 1 : 0;
+            mine += und ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if ((threadIdx.x & 63) == 0) cnt[threadIdx.x >> 6] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+        for (int w = 0; w < waves; ++w) total += cnt[w];
+        row_count[row] = total;
+    }
+}
+
 // row_start[q] = sum of row_count[0 .. q - 1], row_start[Q] = count[0] = the total: ONE workgroup, thread t owns the rows
 // [t * per, (t + 1) * per); integers, so the result does not depend on how the sum is bracketed
 __global__ __launch_bounds__(1024) void undecided_scan_kernel(const int* __restrict__ row_count, int64_t Q, int64_t* __restrict__ row_start,
@@ -412,6 +529,40 @@ extern "C" int cir_rank_undecided(const float* values, int64_t ld, const unsigne
     const size_t lds = (size_t)pow2 * sizeof(RankPair) < 128 ? 128 : (size_t)pow2 * sizeof(RankPair);
     hipLaunchKernelGGL(undecided_flag_kernel, dim3((unsigned)Q), dim3(pow2 >= 2048 ? 1024 : 256), lds, s, values, ld, active, 2.f * margin, K, flags,
                        row_count);
+    hipLaunchKernelGGL(undecided_scan_kernel, dim3(1), dim3(1024), 0, s, row_count, (int64_t)Q, row_start, count);
+    hipLaunchKernelGGL(undecided_emit_kernel, dim3((unsigned)Q), dim3(256), 0, s, flags, row_count, row_start, K, pos);
+    CIR_LAUNCH_RESULT();
+}
+
+extern "C" int cir_rank_undecided_cuts(const float* values, int64_t ld, const unsigned char* active, float margin, int first, const int* cuts,
+                                       int n_cuts, int64_t* pos, int64_t* count, int Q, int K, void* workspace, int64_t workspace_bytes,
+                                       void* stream) {
+    using namespace cir;
+    CIR_CHECK_PTR(values); CIR_CHECK_PTR(pos); CIR_CHECK_PTR(count);
+    if (ld < K || !(margin >= 0.f) || !(margin <= 3.402823466e38f)) return CIR_EINVAL;      // (a NaN margin fails both comparisons)
+    if (first < 0 || n_cuts < 0 || n_cuts > 8 || (n_cuts > 0 && cuts == nullptr)) return CIR_EINVAL;
+    for (int i = 0; i < n_cuts; ++i)
+        if (cuts[i] < 1 || (i > 0 && cuts[i] <= cuts[i - 1])) return CIR_EINVAL;
+    UndecidedPlan plan;
+    const int code = undecided_plan(Q, K, &plan);
+    if (code != CIR_OK) return code;
+    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) != 0 || workspace_bytes < plan.bytes) return CIR_EINVAL;
+    UndecidedBounds bounds;
+    bounds.first = first < K ? first : K;
+    bounds.n = 0;
+    for (int b = 0; b < 9; ++b) bounds.bound[b] = 0;
+    if (first >= 1 && first <= K - 1) bounds.bound[bounds.n++] = first;
+    for (int i = 0; i < n_cuts; ++i)
+        if (cuts[i] <= K - 1) bounds.bound[bounds.n++] = cuts[i];
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    unsigned char* flags = reinterpret_cast<unsigned char*>(workspace);
+    int* row_count = reinterpret_cast<int*>(flags + plan.off_count);
+    int64_t* row_start = reinterpret_cast<int64_t*>(flags + plan.off_start);
+    const int pow2 = rank_pow2(K);
+    const size_t floor_bytes = ((size_t)CUTS_LDS_INTS * sizeof(int) + 127) & ~(size_t)127;
+    const size_t lds = (size_t)pow2 * sizeof(RankPair) < floor_bytes ? floor_bytes : (size_t)pow2 * sizeof(RankPair);
+    hipLaunchKernelGGL(undecided_cuts_flag_kernel, dim3((unsigned)Q), dim3(pow2 >= 2048 ? 1024 : 256), lds, s, values, ld, active, 2.f * margin, K,
+                       bounds, flags, row_count);
     hipLaunchKernelGGL(undecided_scan_kernel, dim3(1), dim3(1024), 0, s, row_count, (int64_t)Q, row_start, count);
     hipLaunchKernelGGL(undecided_emit_kernel, dim3((unsigned)Q), dim3(256), 0, s, flags, row_count, row_start, K, pos);
     CIR_LAUNCH_RESULT();

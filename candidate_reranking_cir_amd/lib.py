@@ -71,6 +71,8 @@ SIGNATURES = {
     "cir_rank_undecided_workspace": (c_int64, [c_int, c_int]),
     "cir_rank_undecided": (c_int, [c_void_p, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "cir_rank_refine_apply": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int, c_int, c_void_p]),
+    "cir_rank_undecided_cuts": (c_int, [c_void_p, c_int64, c_void_p, c_float, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                        c_int64, c_void_p]),
     "cir_linear_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "cir_l2_normalize": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     # training-mode operators

@@ -5,6 +5,7 @@ torch tensors that own the memory.  Nothing here computes with torch ops; there 
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import torch
@@ -667,16 +668,20 @@ def _refine_rows(logits: torch.Tensor):
     return logits.shape
 
 
-def rank_undecided(logits: torch.Tensor, margin: float, active: Optional[torch.Tensor] = None):
+def rank_undecided(logits: torch.Tensor, margin: float, active: Optional[torch.Tensor] = None, *, first: Optional[int] = None, cuts=()):
     """Which entries of the fast logits (Q, K <= 8192) the fast mode cannot order (cir_rank_undecided): an entry within 2 * margin (fp32) of a
     neighbour of its row sorted in argsort_desc's order.  `active` (Q,) uint8 / bool: a row whose byte is 0 yields nothing.  -> (pos, count):
     pos int64 (Q * K,), whose first count[0] elements are the flat positions q * K + k in ascending order (the rest is not written); count
-    int64 (1,), on the device - reading it is the caller's one host read."""
+    int64 (1,), on the device - reading it is the caller's one host read.
+    `first` / `cuts` (cir_rank_undecided_cuts): only the clusters of linked entries that reach into the first `first` places or straddle one of
+    up to 8 strictly ascending cut-offs - what certifies the order of the first places and the sets before each cut.  first=None without cuts
+    is the full rule, through the old entry point; first=None with cuts means first=0."""
     q, k = _refine_rows(logits)
     _need_cuda(active)
     if active is not None:
         active = (active.view(torch.uint8) if active.dtype == torch.bool else active).contiguous()
         assert active.dtype == torch.uint8 and active.shape == (q,)
+    cuts = tuple(int(x) for x in cuts)
     c = _lib.load()
     need = c.cir_rank_undecided_workspace(q, k)
     if need < 0:
@@ -684,9 +689,15 @@ def rank_undecided(logits: torch.Tensor, margin: float, active: Optional[torch.T
     work = torch.empty(need, dtype=torch.uint8, device=logits.device)
     pos = torch.empty(q * k, dtype=torch.int64, device=logits.device)
     count = torch.empty(1, dtype=torch.int64, device=logits.device)
-    code = c.cir_rank_undecided(logits.data_ptr(), logits.stride(0), _ptr(active), float(margin), pos.data_ptr(), count.data_ptr(), q, k,
-                                work.data_ptr(), need, _stream())
-    _lib.check(code, "cir_rank_undecided")
+    if first is None and not cuts:
+        code = c.cir_rank_undecided(logits.data_ptr(), logits.stride(0), _ptr(active), float(margin), pos.data_ptr(), count.data_ptr(), q, k,
+                                    work.data_ptr(), need, _stream())
+        _lib.check(code, "cir_rank_undecided")
+        return pos, count
+    host_cuts = (ctypes.c_int * max(len(cuts), 1))(*cuts)
+    code = c.cir_rank_undecided_cuts(logits.data_ptr(), logits.stride(0), _ptr(active), float(margin), int(first or 0), host_cuts, len(cuts),
+                                     pos.data_ptr(), count.data_ptr(), q, k, work.data_ptr(), need, _stream())
+    _lib.check(code, "cir_rank_undecided_cuts")
     return pos, count
 
 

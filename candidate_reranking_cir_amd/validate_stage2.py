@@ -26,6 +26,8 @@ from . import ops
 from .blip_stage2 import encode_text
 
 SKIP_FILL = -99999.99
+# the cut-offs the metric functions read: Recall@1/5/10/50 (compute_cirr_val_metrics), Recall@10/50 (compute_fiq_val_metrics)
+RECALL_CUTS = {"cirr": (1, 5, 10, 50), "fiq": (10, 50)}
 
 
 @dataclass
@@ -118,19 +120,22 @@ def _check_bank_rows(ds: RelativeValSet, n_index: int):
 def generate_val_predictions(blip_model, model_stage1, ds: RelativeValSet, index_features: torch.Tensor,
                              query_batch: int = 8, rows: Optional[Sequence[int]] = None, kv_bank: Optional[list] = None, *,
                              refine_margin: Optional[float] = None, referee_index_features: Optional[torch.Tensor] = None,
-                             referee=None, on_violation: str = "warn", refine_stats: Optional[dict] = None):
+                             referee=None, on_violation: str = "warn", refine_stats: Optional[dict] = None,
+                             refine_first: Optional[int] = None, refine_cuts: Sequence[int] = ()):
     """Logits (len(rows), K) [and (len(rows), 5) subset logits when `ds.group_index` is set].
     `rows` selects a shard of the queries (default: all).  `kv_bank` (blip_model.build_kv_bank(index_features))
     re-uses the per-image cross-attention K/V across all queries instead of re-projecting every candidate.
     `refine_margin` (opt-in; None = this function as it always was): the logits then go through `refine_predictions` with the exact-mode
-    bank `referee_index_features` (and `referee`, `on_violation` as there); `refine_stats`, a dict, receives its statistics."""
+    bank `referee_index_features` (and `referee`, `on_violation` as there); `refine_stats`, a dict, receives its statistics;
+    `refine_first` / `refine_cuts` are its `first` / `cuts` (e.g. RECALL_CUTS["cirr"]): certify the first places and the recall cut-offs only."""
     if refine_margin is not None:
         if referee_index_features is None:
             raise ValueError("refine_margin needs referee_index_features: extract_index_features on the referee model (the exact-mode fp32 bank)")
         out = generate_val_predictions(blip_model, model_stage1, ds, index_features, query_batch, rows, kv_bank)
         logits, glogits = out if ds.group_index is not None else (out, None)
         logits, glogits, stats = refine_predictions(blip_model, model_stage1, ds, logits, glogits, referee_index_features, refine_margin,
-                                                    referee=referee, query_batch=query_batch, rows=rows, on_violation=on_violation)
+                                                    referee=referee, query_batch=query_batch, rows=rows, on_violation=on_violation,
+                                                    first=refine_first, cuts=refine_cuts)
         if refine_stats is not None:
             refine_stats.update(stats)
         return (logits, glogits) if glogits is not None else logits
@@ -195,7 +200,7 @@ def _referee_pair(blip_model, model_stage1, referee):
 @torch.no_grad()
 def refine_predictions(blip_model, model_stage1, ds: RelativeValSet, logits: torch.Tensor, glogits: Optional[torch.Tensor],
                        referee_index_features: torch.Tensor, margin: float, *, referee=None, query_batch: int = 8,
-                       rows: Optional[Sequence[int]] = None, on_violation: str = "warn"):
+                       rows: Optional[Sequence[int]] = None, on_violation: str = "warn", first: Optional[int] = None, cuts: Sequence[int] = ()):
     """Phase 2 of a fast-mode run: the exact mode scores again only the entries whose order the fast logits cannot decide, and overwrites
     them IN PLACE.  `logits` (len(rows), K) and `glogits` (len(rows), 5) or None are `generate_val_predictions`' outputs for the same `ds`
     and `rows`, from models in any fast precision.
@@ -206,6 +211,12 @@ def refine_predictions(blip_model, model_stage1, ds: RelativeValSet, logits: tor
     code, which only sort the matrix (validate_stage2.py:53, 174, 188), give the exact mode's results.  The guarantee is conditional on the
     margin (`calibrate_margin`); `stats` reports at run time whether it held on the entries that were re-scored.
 
+    `first` / `cuts` (cir_rank_undecided_cuts; default: the full rule above): nobody reads every position - Recall@c depends on WHICH entries
+    hold the first c places (RECALL_CUTS), a top-k list on the first k places.  A cluster (maximal run of linked places [a, b]) of the (Q, K)
+    matrix is then re-scored only if a < first or a < c <= b for a cut c (up to 8, strictly ascending, >= 1).  Under the same condition the
+    first min(first, K) places of the refined row hold the exact row's columns, and the set of columns before every cut c < K is the exact
+    row's.  The (Q, 5) subset matrix keeps the full rule: Recall_subset@1/2/3 reads its order.
+
     `referee_index_features`: the exact-mode bank, `extract_index_features(images, referee_model)` (fp32); the caller builds it once.
     `referee`: (stage-II referee, stage-I referee) as `model.referee()` returns them; None builds the pair here - and only when at least one
     entry is undecided (margin 0 on rows without ties packs and launches nothing).  Pass the pair to keep its packed engines across calls.
@@ -213,7 +224,8 @@ def refine_predictions(blip_model, model_stage1, ds: RelativeValSet, logits: tor
     undecided positions are copied once to group them by query and by caption length like phase 1; z_t is formed once per affected query.
 
     -> (logits, glogits, stats); stats: `entries` (of all scored rows), `rescored`, `queries_rescored`, `max_deviation` (max |fast - exact|
-    over the re-scored entries), `violations` (how many of them exceed `margin`) and `margin`.  violations > 0 means the bound was wrong
+    over the re-scored entries), `violations` (how many of them exceed `margin`), `margin`, `first`, `cuts` and `certified` (what the run
+    certifies when violations == 0, in words).  violations > 0 means the bound was wrong
     for this data and the order is NOT certified: one warning (`on_violation="warn"`) or `RefineBoundError` ("raise"; the matrices are
     already overwritten then)."""
     margin = float(margin)
@@ -221,6 +233,13 @@ def refine_predictions(blip_model, model_stage1, ds: RelativeValSet, logits: tor
         raise ValueError(f"refine_predictions: margin {margin} (finite and >= 0)")
     if on_violation not in ("warn", "raise"):
         raise ValueError('on_violation is "warn" or "raise"')
+    cuts = tuple(int(c) for c in cuts)
+    if first is not None and int(first) < 0:
+        raise ValueError(f"refine_predictions: first {first} (>= 0)")
+    if len(cuts) > 8 or any(c < 1 for c in cuts) or any(b <= a for a, b in zip(cuts, cuts[1:])):
+        raise ValueError(f"refine_predictions: cuts {cuts} (at most 8, each >= 1, strictly ascending)")
+    full = first is None and not cuts
+    first = None if full else int(first or 0)
     dev = logits.device
     rows = list(range(len(ds))) if rows is None else list(rows)
     if logits.shape != (len(rows), ds.K) or (glogits is not None and (ds.group_index is None or glogits.shape != (len(rows), ds.group_index.shape[1]))):
@@ -233,9 +252,17 @@ def refine_predictions(blip_model, model_stage1, ds: RelativeValSet, logits: tor
     if glogits is not None:
         mats.append((glogits, None, ds.group_index))                     # every query's subset is scored (validate_stage2.py:261-269)
         entries += glogits.numel()
-    found = [ops.rank_undecided(m, margin, act) for m, act, _ in mats]
+    found = [ops.rank_undecided(m, margin, act) if full or i else ops.rank_undecided(m, margin, act, first=first, cuts=cuts)
+             for i, (m, act, _) in enumerate(mats)]                     # (the subset matrix, i = 1: always the full rule)
     counts = [int(c) for _, c in found]                                  # the host reads: one count per matrix
-    stats = dict(entries=entries, rescored=sum(counts), queries_rescored=0, max_deviation=0.0, violations=0, margin=margin)
+    if full:
+        certified = "every position of every row sorts as the exact mode's"
+    else:
+        certified = (f"the first {min(first, ds.K)} places of every row hold the exact mode's columns"
+                     + (f"; the sets before the cuts {tuple(c for c in cuts if c < ds.K)} are the exact mode's" if cuts else "")
+                     + ("; every position of the subset rows sorts as the exact mode's" if glogits is not None else ""))
+    stats = dict(entries=entries, rescored=sum(counts), queries_rescored=0, max_deviation=0.0, violations=0, margin=margin,
+                 first=first, cuts=cuts, certified=certified)
     if sum(counts) == 0:
         return logits, glogits, stats
     _check_bank_rows(ds, referee_index_features.shape[0])

@@ -385,7 +385,7 @@ int cir_topk_select(const float* values, int64_t ld, const int64_t* exclude, int
 int cir_rank_of(const float* values, int64_t ld, const int64_t* cols, const int64_t* exclude, int64_t* rank, int Q, int n, int m, void* stream);
 
 /*
- * Rank refinement (csrc/rank.hip; three entry points, additive within ABI v15 like cir_topk_select): a fast precision mode's logits decide the
+ * Rank refinement (csrc/rank.hip; four entry points, additive within ABI v15 like cir_topk_select; 66 entry points in all): a fast precision mode's logits decide the
  * order of a row wherever two values are far enough apart; only the rest is scored again by the exact mode.  Consumers of a logits matrix only
  * ever sort its rows (validate_stage2.py:53, 174, 188), so the matrix with the undecided entries overwritten sorts as the exact mode's.
  * The rule, for a row s and a margin >= 0, width = 2 * margin (exact in fp32): sort the row in cir_topk_desc's order (value descending, ties to
@@ -407,12 +407,24 @@ int cir_rank_of(const float* values, int64_t ld, const int64_t* cols, const int6
  *   written but stats).  stats: 16 bytes on the device, 8-byte aligned: fp32 max_i |old - referee| at byte 0 (a difference that is not a number
  *   does not enter the maximum), int64 at byte 8 the number of i that fail |old - referee| <= margin - the run-time check of the bound on
  *   exactly the entries it matters for.  A position outside [0, Q * K) is not written and counts as failing.  One workgroup, fixed-order reduction.
+ * cir_rank_undecided_cuts (validate.py:60-64, 218-226; cirr_test_submission_stage2.py: the first 50 names): cir_rank_undecided for consumers that
+ *   read only the first places of a row in order and the SETS before a few recall cut-offs.  A cluster is a maximal run [a, b] of linked places
+ *   of the sorted row; with first >= 0 and up to 8 strictly ascending cuts >= 1 (a HOST array of n_cuts int32, copied into the kernel arguments;
+ *   may be NULL when n_cuts = 0), a cluster is selected iff b > a and (a < first, or a < c <= b for some cut c); an entry is undecided iff its
+ *   cluster is selected.  first >= K selects every cluster (cir_rank_undecided's rule); a cut >= K selects nothing; first = 0 without cuts selects
+ *   nothing.  If |fast - exact| <= margin on every entry of the row, places 0 .. min(first, K) - 1 of the stable descending argsort of the refined
+ *   row hold the exact row's columns, and for every cut c < K the set of columns in places 0 .. c - 1 is the exact row's.
+ *   first < 0, n_cuts outside 0 .. 8, a cut < 1 or cuts not strictly ascending: CIR_EINVAL, before any launch.  values, ld, active, margin, pos,
+ *   count, K <= 8192, the workspace (cir_rank_undecided_workspace) and the three launches are cir_rank_undecided's; the flag pass adds integer
+ *   max / min reductions over the workgroup for the clusters that straddle a boundary.  Same input, same pos and count, bit for bit.
  */
 int64_t cir_rank_undecided_workspace(int Q, int K);
 int cir_rank_undecided(const float* values, int64_t ld, const unsigned char* active, float margin, int64_t* pos, int64_t* count, int Q, int K,
                        void* workspace, int64_t workspace_bytes, void* stream);
 int cir_rank_refine_apply(float* values, int64_t ld, const int64_t* pos, const float* referee, int64_t n, float margin, void* stats, int Q, int K,
                           void* stream);
+int cir_rank_undecided_cuts(const float* values, int64_t ld, const unsigned char* active, float margin, int first, const int* cuts, int n_cuts,
+                            int64_t* pos, int64_t* count, int Q, int K, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * fp32 y (M,N) = x (M,K) W(N,K)^T + bias (mode 0), 1 - x W^T (mode 1) or x W^T - 1 (mode 2, the exact
