@@ -206,38 +206,6 @@ __global__ __launch_bounds__(256) void l2_normalize_kernel(const float* x, float
     for (int c = lane; c < cols; c += 64) y[row * cols + c] = x[row * cols + c] * inv;
 }
 
-// ---- descending argsort of one row per workgroup: bitonic network on (value, index) in LDS ------------------
-__global__ __launch_bounds__(256) void topk_desc_kernel(const float* logits, int64_t* idx, int K, int n_pow2) {
-    extern __shared__ __attribute__((aligned(16))) char dyn[];
-    float* val = reinterpret_cast<float*>(dyn);
-    int* ind = reinterpret_cast<int*>(dyn + (size_t)n_pow2 * 4);
-    const float* row = logits + (int64_t)blockIdx.x * K;
-    for (int i = threadIdx.x; i < n_pow2; i += blockDim.x) {
-        float v = i < K ? row[i] : -INFINITY;
-        if (v != v) v = -INFINITY;  // NaN sorts last
-        val[i] = v;
-        ind[i] = i < K ? i : 0x7fffffff;
-    }
-    __syncthreads();
-    // "a before b" <=> a.val > b.val, or equal values and a.idx < b.idx (padding has idx = INT_MAX)
-    for (int size = 2; size <= n_pow2; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = threadIdx.x; t < n_pow2 / 2; t += blockDim.x) {
-                const int lo = 2 * t - (t & (stride - 1));
-                const int hi = lo + stride;
-                const bool asc_block = ((lo & size) != 0);  // alternate direction to build bitonic runs
-                const float va = val[lo], vb = val[hi];
-                const int ia = ind[lo], ib = ind[hi];
-                const bool a_first = (va > vb) || (va == vb && ia < ib);
-                const bool swap = asc_block ? a_first : !a_first;
-                if (swap) { val[lo] = vb; val[hi] = va; ind[lo] = ib; ind[hi] = ia; }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) idx[(int64_t)blockIdx.x * K + i] = ind[i];
-}
-
 }  // namespace cir
 
 extern "C" int cir_version(void) { return CIR_ABI_VERSION; }
@@ -322,17 +290,6 @@ extern "C" int cir_small_linear(const void* x, int64_t ldx, const void* W, const
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dtype == CIR_BF16) hipLaunchKernelGGL((small_linear_kernel<__bf16>), grid, block, 0, s, (const __bf16*)x, ldx, (const __bf16*)W, bias, y, M, N, K);
     else hipLaunchKernelGGL((small_linear_kernel<_Float16>), grid, block, 0, s, (const _Float16*)x, ldx, (const _Float16*)W, bias, y, M, N, K);
-    CIR_LAUNCH_RESULT();
-}
-
-extern "C" int cir_topk_desc(const float* logits, int64_t* idx, int Q, int K, void* stream) {
-    CIR_CHECK_PTR(logits); CIR_CHECK_PTR(idx);
-    if (Q <= 0 || K <= 0) return CIR_EINVAL;
-    if (K > 8192) return CIR_ESHAPE;   // 8192 (value, index) pairs = 64 KiB of LDS: every index of the reference's datasets fits
-    int n = 2;
-    while (n < K) n <<= 1;
-    dim3 grid((unsigned)Q), block(256);
-    hipLaunchKernelGGL(cir::topk_desc_kernel, grid, block, (size_t)n * 8, reinterpret_cast<hipStream_t>(stream), logits, idx, K, n);
     CIR_LAUNCH_RESULT();
 }
 

@@ -1,19 +1,24 @@
+// The per-row sorts of the library: one bitonic network on (value, column) pairs in LDS (rank_sort_first), one order - a before b <=>
+// a.val > b.val, or equal values and a.idx < b.idx; a NaN reads as -inf; an excluded column does not exist.  That order is strict and
+// total, so every result below is unique.
+//
+// cir_topk_desc: the whole order of rows of at most 8192 columns - level 1 below on one segment with k = n, which keeps every place.
+//
 // Stage-I retrieval over an index of any size: the first k columns of every row's descending order (cir_topk_select) and the place of
 // a few given columns in that order (cir_rank_of) - what stage II reads of a full ranking (validate.py:57-64, 202-226), without the
-// 8192-column ceiling of cir_topk_desc's one-row-per-workgroup sort.
-//
-// The order is topk_desc_kernel's (misc.hip): a before b <=> a.val > b.val, or equal values and a.idx < b.idx; a NaN reads as -inf; an
-// excluded column does not exist.  That order is strict and total, so "the first k of a row" is one well-defined list and
+// 8192-column ceiling of one workgroup's sort.  Because the order is total,
 //   first_k(row) = first_k(union over segments of first_k(segment))
 // holds exactly - ties across segment seams, NaNs, +-inf and exclusions included.  Level 1 sorts each segment of at most 8192 columns in
 // LDS and keeps its first k (value, column) pairs; level 2 sorts groups of floor(8192 / k) such lists the same way until one is left.
 // Lists are always k pairs long: missing places hold the padding pair (-inf, INT_MAX), which comes after every real column (columns are
-// below 2^31 - 1) and never reaches the result, because k <= n - 1 real columns exist in every row.
+// below 2^31 - 1) and never reaches the result: cir_topk_select has k <= n - 1 real columns in every row, and cir_topk_desc's one segment
+// holds exactly k = n real pairs before its padding.
 //
 // Rank refinement (cir_rank_undecided, cir_rank_refine_apply; validate_stage2.py:53, 174, 188): the same sort and order, on rows of at most
 // 8192 logits of a fast precision mode - which entries lie within 2 * margin of a neighbour of the sorted row, so that only they are scored
 // again by the exact mode, and the write-back of those scores with a check of the margin on the values they replace.  cir_rank_undecided_cuts
-// keeps of them only the runs of linked places that reach into the first places or straddle a recall cut-off: what top-k lists and Recall@c read.
+// keeps of them only the runs of linked places that reach into the first places or straddle a recall cut-off: what top-k lists and Recall@c
+// read.  The two entry points share the host path and the scan and emit launches; each has its own flag kernel.
 #include "common.hpp"
 
 namespace cir {
@@ -26,8 +31,13 @@ struct __attribute__((aligned(8))) RankPair { float v; int i; };
 __device__ __forceinline__ bool rank_before(float va, int ia, float vb, int ib) { return (va > vb) || (va == vb && ia < ib); }
 __device__ __forceinline__ float rank_key(float v) { return v != v ? -INFINITY : v; }   // NaN sorts last
 
+// the pairs one workgroup sorts for n of them.  The host sizes LDS and the block by it and hands it to the two levels of cir_topk_select, which
+// ask again only for a row's last segment or group of lists: it may be shorter than the others
+__host__ __device__ inline int rank_pow2(int n) { int p = 2; while (p < n) p <<= 1; return p; }
+static dim3 rank_block(int pow2) { return dim3(pow2 >= 2048 ? 1024 : 256); }
+
 // The first `first` places of the sorted order, in place (first: a power of two, 2 <= first <= n_pow2; every thread of the workgroup calls it).
-// Phase 1 is the bitonic network of topk_desc_kernel on interleaved pairs (one 8-byte LDS access per pair), stopped at runs of `first`: they
+// Phase 1 is the bitonic network on interleaved pairs (one 8-byte LDS access per pair), stopped at runs of `first`: they
 // come out alternately descending and ascending.  Phase 2 halves the number of runs until one is left: a descending run and its ascending
 // neighbour form a bitonic sequence, so the pairwise winners (place i against place i, `span` apart) are the `first` leading pairs of the two
 // runs and bitonic again; one merge pass (strides first / 2 .. 1) sorts them, descending or ascending by the run's new number.  Only winners
@@ -81,16 +91,15 @@ __device__ __forceinline__ void rank_emit(const RankPair* p, int n_pow2, int k, 
 
 // ---- level 1: one workgroup per (row, segment); blockIdx.x = row * segs + segment ----
 __global__ __launch_bounds__(1024) void topk_segment_kernel(const float* __restrict__ values, int64_t ld, const int64_t* __restrict__ exclude, int n, int k,
-                                                            int segs, RankPair* __restrict__ lists, int64_t* __restrict__ idx, float* __restrict__ val) {
+                                                            int seg_pow2, int keep, int segs, RankPair* __restrict__ lists,
+                                                            int64_t* __restrict__ idx, float* __restrict__ val) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     RankPair* p = reinterpret_cast<RankPair*>(dyn);
     const int64_t row = blockIdx.x / (unsigned)segs;
     const int seg = (int)(blockIdx.x - row * segs);
     const int c0 = seg * RANK_SEG;                      // < n
     const int len = min(n - c0, RANK_SEG);
-    int n_pow2 = 2, keep = 2;
-    while (n_pow2 < len) n_pow2 <<= 1;
-    while (keep < k) keep <<= 1;
+    const int n_pow2 = seg + 1 < segs || segs == 1 ? seg_pow2 : rank_pow2(len);     // only the last of several segments is shorter than the host's
     const int64_t ex = exclude != nullptr ? exclude[row] : -1;
     const float* src = values + row * ld + c0;
     for (int i = threadIdx.x; i < n_pow2; i += blockDim.x) {
@@ -106,7 +115,7 @@ __global__ __launch_bounds__(1024) void topk_segment_kernel(const float* __restr
 }
 
 // ---- level 2: one workgroup per (row, group of at most `group` lists); blockIdx.x = row * lists_out + g; group * k <= 8192 ----
-__global__ __launch_bounds__(1024) void topk_merge_kernel(const RankPair* __restrict__ in, int lists_in, int group, int lists_out, int k,
+__global__ __launch_bounds__(1024) void topk_merge_kernel(const RankPair* __restrict__ in, int lists_in, int group, int lists_out, int k, int grp_pow2, int keep,
                                                           RankPair* __restrict__ out, int64_t* __restrict__ idx, float* __restrict__ val) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     RankPair* p = reinterpret_cast<RankPair*>(dyn);
@@ -114,9 +123,7 @@ __global__ __launch_bounds__(1024) void topk_merge_kernel(const RankPair* __rest
     const int g = (int)(blockIdx.x - row * lists_out);
     const int first = g * group;
     const int cnt = min(group, lists_in - first) * k;
-    int n_pow2 = 2, keep = 2;
-    while (n_pow2 < cnt) n_pow2 <<= 1;
-    while (keep < k) keep <<= 1;
+    const int n_pow2 = g + 1 < lists_out || lists_out == 1 ? grp_pow2 : rank_pow2(cnt);     // as for level 1's last segment
     const RankPair* src = in + (row * lists_in + first) * k;
     for (int i = threadIdx.x; i < n_pow2; i += blockDim.x) {
         RankPair e;
@@ -465,9 +472,20 @@ static int rank_plan(int64_t Q, int64_t n, int64_t k, RankPlan* plan) {
     return CIR_OK;
 }
 
-static int rank_pow2(int n) { int p = 2; while (p < n) p <<= 1; return p; }
-
 }  // namespace cir
+
+// the whole order of a row: level 1 on one segment with k = n, so rank_sort_first keeps every place; the K real pairs come before the padding,
+// so places 0 .. K - 1 are real.  Not through rank_plan: its k <= n - 1 belongs to cir_topk_select's lists.
+extern "C" int cir_topk_desc(const float* logits, int64_t* idx, int Q, int K, void* stream) {
+    using namespace cir;
+    CIR_CHECK_PTR(logits); CIR_CHECK_PTR(idx);
+    if (Q <= 0 || K <= 0) return CIR_EINVAL;
+    if (K > RANK_SEG) return CIR_ESHAPE;   // every index of the reference's datasets fits
+    const int pow2 = rank_pow2(K);
+    hipLaunchKernelGGL(topk_segment_kernel, dim3((unsigned)Q), rank_block(pow2), (size_t)pow2 * sizeof(RankPair), reinterpret_cast<hipStream_t>(stream),
+                       logits, (int64_t)K, nullptr, K, K, pow2, pow2, 1, nullptr, idx, nullptr);
+    CIR_LAUNCH_RESULT();
+}
 
 extern "C" int64_t cir_topk_select_workspace(int Q, int n, int k) {
     cir::RankPlan plan;
@@ -489,16 +507,17 @@ extern "C" int cir_topk_select(const float* values, int64_t ld, const int64_t* e
     RankPair* buf_a = reinterpret_cast<RankPair*>(workspace);
     RankPair* buf_b = reinterpret_cast<RankPair*>(reinterpret_cast<char*>(workspace) + plan.bytes_a);
     {
-        dim3 grid((unsigned)((int64_t)Q * plan.segs)), block(seg_pow2 >= 2048 ? 1024 : 256);
-        hipLaunchKernelGGL(topk_segment_kernel, grid, block, (size_t)seg_pow2 * sizeof(RankPair), s, values, ld, exclude, n, k, plan.segs,
+        dim3 grid((unsigned)((int64_t)Q * plan.segs));
+        hipLaunchKernelGGL(topk_segment_kernel, grid, rank_block(seg_pow2), (size_t)seg_pow2 * sizeof(RankPair), s, values, ld, exclude, n, k,
+                           seg_pow2, rank_pow2(k), plan.segs,
                            plan.segs > 1 ? buf_a : nullptr, idx, val);
     }
     RankPair *in = buf_a, *out = buf_b;
     for (int lists = plan.segs; lists > 1;) {
         const int lists_out = (lists + plan.group - 1) / plan.group;
         const int pow2 = rank_pow2((lists < plan.group ? lists : plan.group) * k);
-        dim3 grid((unsigned)((int64_t)Q * lists_out)), block(pow2 >= 2048 ? 1024 : 256);
-        hipLaunchKernelGGL(topk_merge_kernel, grid, block, (size_t)pow2 * sizeof(RankPair), s, in, lists, plan.group, lists_out, k,
+        dim3 grid((unsigned)((int64_t)Q * lists_out));
+        hipLaunchKernelGGL(topk_merge_kernel, grid, rank_block(pow2), (size_t)pow2 * sizeof(RankPair), s, in, lists, plan.group, lists_out, k, pow2, rank_pow2(k),
                            lists_out > 1 ? out : nullptr, idx, val);
         RankPair* t = in; in = out; out = t;
         lists = lists_out;
@@ -512,11 +531,11 @@ extern "C" int64_t cir_rank_undecided_workspace(int Q, int K) {
     return code != CIR_OK ? (int64_t)code : plan.bytes;
 }
 
-extern "C" int cir_rank_undecided(const float* values, int64_t ld, const unsigned char* active, float margin, int64_t* pos, int64_t* count,
-                                  int Q, int K, void* workspace, int64_t workspace_bytes, void* stream) {
+// both rank_undecided entry points, after their argument checks: the extents' refusals, the workspace, the three launches.
+// bounds == nullptr: the full rule's flag kernel
+static int rank_undecided_launch(const float* values, int64_t ld, const unsigned char* active, float margin, const cir::UndecidedBounds* bounds,
+                                 int64_t* pos, int64_t* count, int Q, int K, void* workspace, int64_t workspace_bytes, void* stream) {
     using namespace cir;
-    CIR_CHECK_PTR(values); CIR_CHECK_PTR(pos); CIR_CHECK_PTR(count);
-    if (ld < K || !(margin >= 0.f) || !(margin <= 3.402823466e38f)) return CIR_EINVAL;      // (a NaN margin fails both comparisons)
     UndecidedPlan plan;
     const int code = undecided_plan(Q, K, &plan);
     if (code != CIR_OK) return code;
@@ -526,46 +545,41 @@ extern "C" int cir_rank_undecided(const float* values, int64_t ld, const unsigne
     int* row_count = reinterpret_cast<int*>(flags + plan.off_count);
     int64_t* row_start = reinterpret_cast<int64_t*>(flags + plan.off_start);
     const int pow2 = rank_pow2(K);
-    const size_t lds = (size_t)pow2 * sizeof(RankPair) < 128 ? 128 : (size_t)pow2 * sizeof(RankPair);
-    hipLaunchKernelGGL(undecided_flag_kernel, dim3((unsigned)Q), dim3(pow2 >= 2048 ? 1024 : 256), lds, s, values, ld, active, 2.f * margin, K, flags,
-                       row_count);
+    const size_t floor_bytes = bounds == nullptr ? 128 : ((size_t)CUTS_LDS_INTS * sizeof(int) + 127) & ~(size_t)127;
+    const size_t lds = (size_t)pow2 * sizeof(RankPair) < floor_bytes ? floor_bytes : (size_t)pow2 * sizeof(RankPair);
+    if (bounds == nullptr)
+        hipLaunchKernelGGL(undecided_flag_kernel, dim3((unsigned)Q), rank_block(pow2), lds, s, values, ld, active, 2.f * margin, K, flags, row_count);
+    else
+        hipLaunchKernelGGL(undecided_cuts_flag_kernel, dim3((unsigned)Q), rank_block(pow2), lds, s, values, ld, active, 2.f * margin, K, *bounds, flags,
+                           row_count);
     hipLaunchKernelGGL(undecided_scan_kernel, dim3(1), dim3(1024), 0, s, row_count, (int64_t)Q, row_start, count);
     hipLaunchKernelGGL(undecided_emit_kernel, dim3((unsigned)Q), dim3(256), 0, s, flags, row_count, row_start, K, pos);
     CIR_LAUNCH_RESULT();
 }
 
+extern "C" int cir_rank_undecided(const float* values, int64_t ld, const unsigned char* active, float margin, int64_t* pos, int64_t* count,
+                                  int Q, int K, void* workspace, int64_t workspace_bytes, void* stream) {
+    CIR_CHECK_PTR(values); CIR_CHECK_PTR(pos); CIR_CHECK_PTR(count);
+    if (ld < K || !(margin >= 0.f) || !(margin <= 3.402823466e38f)) return CIR_EINVAL;      // (a NaN margin fails both comparisons)
+    return rank_undecided_launch(values, ld, active, margin, nullptr, pos, count, Q, K, workspace, workspace_bytes, stream);
+}
+
 extern "C" int cir_rank_undecided_cuts(const float* values, int64_t ld, const unsigned char* active, float margin, int first, const int* cuts,
                                        int n_cuts, int64_t* pos, int64_t* count, int Q, int K, void* workspace, int64_t workspace_bytes,
                                        void* stream) {
-    using namespace cir;
     CIR_CHECK_PTR(values); CIR_CHECK_PTR(pos); CIR_CHECK_PTR(count);
     if (ld < K || !(margin >= 0.f) || !(margin <= 3.402823466e38f)) return CIR_EINVAL;      // (a NaN margin fails both comparisons)
     if (first < 0 || n_cuts < 0 || n_cuts > 8 || (n_cuts > 0 && cuts == nullptr)) return CIR_EINVAL;
     for (int i = 0; i < n_cuts; ++i)
         if (cuts[i] < 1 || (i > 0 && cuts[i] <= cuts[i - 1])) return CIR_EINVAL;
-    UndecidedPlan plan;
-    const int code = undecided_plan(Q, K, &plan);
-    if (code != CIR_OK) return code;
-    if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7u) != 0 || workspace_bytes < plan.bytes) return CIR_EINVAL;
-    UndecidedBounds bounds;
+    cir::UndecidedBounds bounds;                                         // (for a K the plan refuses: never launched)
     bounds.first = first < K ? first : K;
     bounds.n = 0;
     for (int b = 0; b < 9; ++b) bounds.bound[b] = 0;
     if (first >= 1 && first <= K - 1) bounds.bound[bounds.n++] = first;
     for (int i = 0; i < n_cuts; ++i)
         if (cuts[i] <= K - 1) bounds.bound[bounds.n++] = cuts[i];
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    unsigned char* flags = reinterpret_cast<unsigned char*>(workspace);
-    int* row_count = reinterpret_cast<int*>(flags + plan.off_count);
-    int64_t* row_start = reinterpret_cast<int64_t*>(flags + plan.off_start);
-    const int pow2 = rank_pow2(K);
-    const size_t floor_bytes = ((size_t)CUTS_LDS_INTS * sizeof(int) + 127) & ~(size_t)127;
-    const size_t lds = (size_t)pow2 * sizeof(RankPair) < floor_bytes ? floor_bytes : (size_t)pow2 * sizeof(RankPair);
-    hipLaunchKernelGGL(undecided_cuts_flag_kernel, dim3((unsigned)Q), dim3(pow2 >= 2048 ? 1024 : 256), lds, s, values, ld, active, 2.f * margin, K,
-                       bounds, flags, row_count);
-    hipLaunchKernelGGL(undecided_scan_kernel, dim3(1), dim3(1024), 0, s, row_count, (int64_t)Q, row_start, count);
-    hipLaunchKernelGGL(undecided_emit_kernel, dim3((unsigned)Q), dim3(256), 0, s, flags, row_count, row_start, K, pos);
-    CIR_LAUNCH_RESULT();
+    return rank_undecided_launch(values, ld, active, margin, &bounds, pos, count, Q, K, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cir_rank_refine_apply(float* values, int64_t ld, const int64_t* pos, const float* referee, int64_t n, float margin, void* stats,

@@ -356,6 +356,7 @@ int cir_gather_rows(const void* src, int src_dtype, const int64_t* index, void* 
  * Per-row descending argsort (validate_stage2.py:53,174,188: torch.argsort(..., descending=True)):
  *   idx[q][j] = index of the j-th largest logit of row q, ties broken by lower index.  K <= 8192
  *   (also ranks a whole index for stage I: validate.py:58, 203 sort ascending distances = descending -distance).
+ * The kernel is cir_topk_select's segment sort (csrc/rank.hip) on one segment with k = n.
  */
 int cir_topk_desc(const float* logits, int64_t* idx, int Q, int K, void* stream);
 

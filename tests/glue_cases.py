@@ -240,7 +240,7 @@ def _l2_bound(c):
 
 # ================================================================================================ cir_topk_desc
 ARGSORT_KINDS = ("random", "all_equal", "levels8", "sorted_desc", "sorted_asc", "signed_zero", "inf", "nan")
-_ARGSORT_K = (1, 2, 3, 255, 256, 257, 2297, 4096, 4097, 6346, 8191, 8192)
+_ARGSORT_K = (1, 2, 3, 255, 256, 257, 2047, 2048, 2297, 4096, 4097, 6346, 8191, 8192)       # one pair; 256 threads up to 1024 columns, 1024 above
 
 
 def _argsort_cases():
@@ -273,7 +273,7 @@ def _argsort_inputs(c):
 
 
 def argsort_ref(logits):
-    """The contract of misc.hip: NaN ranks as -inf; among equal values (NaN and -inf alike) the lower index comes first."""
+    """The contract of cir_topk_desc: NaN ranks as -inf; among equal values (NaN and -inf alike) the lower index comes first."""
     v = torch.where(logits != logits, torch.full_like(logits, -math.inf), logits)
     return torch.argsort(v, dim=-1, descending=True, stable=True)
 

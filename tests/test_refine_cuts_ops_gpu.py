@@ -103,7 +103,7 @@ def _undecided_cuts(rt, view, margin, active, first, cuts):
     return pbig.cpu(), int(count.cpu()[0])
 
 
-@pytest.mark.parametrize("k", [1, 2, 5, 24, 100, 105, 257, 1024, 1025, 8192])
+@pytest.mark.parametrize("k", [1, 2, 5, 24, 100, 105, 257, 1024, 1025, 2047, 2048, 8192])
 @pytest.mark.parametrize("q", [1, 3, 70])
 def test_selected_against_the_restatement(rt, q, k):
     v, margin, active = _case(q, k)

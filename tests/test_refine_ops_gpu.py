@@ -100,7 +100,7 @@ def _undecided(rt, view, margin, active):
     return pbig.cpu(), int(count.cpu()[0])
 
 
-@pytest.mark.parametrize("k", [1, 2, 5, 63, 64, 65, 100, 1025, 8192])
+@pytest.mark.parametrize("k", [1, 2, 5, 63, 64, 65, 100, 1025, 2047, 2048, 8192])
 @pytest.mark.parametrize("q", [1, 3, 65])
 def test_undecided_against_the_restatement(rt, q, k):
     v, margin, active = _case(q, k)

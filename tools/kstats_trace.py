@@ -24,13 +24,13 @@ def main():
             if not in_vit:
                 starts.append(i)
             in_vit = True
-        elif "topk_desc_kernel" in name:
+        elif "topk_segment_kernel" in name:
             in_vit = False
     if len(starts) < warmup + steps:
         raise SystemExit(f"found {len(starts)} steps in the trace, need {warmup + steps}")
     lo, hi = starts[warmup], (starts[warmup + steps] if len(starts) > warmup + steps else len(rows))
     # the timed region ends with the last step's top-k launches: cut the tail at the last topk before `hi`
-    while hi > lo and "topk_desc_kernel" not in rows[hi - 1][2]:
+    while hi > lo and "topk_segment_kernel" not in rows[hi - 1][2]:
         hi -= 1
     sel = rows[lo:hi]
     agg = {}

@@ -59,7 +59,7 @@ def canonical(name: str):
         if short in name:
             return f"cir::{short}"
     for short in ("attn_shared_kernel", "attn_stream_kernel", "layernorm_h16_kernel", "layernorm_kernel", "embed_ln_kernel", "patchify_kernel", "vit_assemble_kernel",
-                  "gather_rows_kernel", "topk_desc_kernel", "small_linear_kernel", "cls_xattn_kernel"):
+                  "gather_rows_kernel", "topk_segment_kernel", "small_linear_kernel", "cls_xattn_kernel"):
         if short in name:
             masked = ""
             if short.startswith("attn"):
