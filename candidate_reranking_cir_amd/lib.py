@@ -16,6 +16,11 @@ CIR_BF16, CIR_F16, CIR_F32 = 0, 1, 2
 TUNE_GEMM_TILE, TUNE_GEMM_GROUP_W, TUNE_ATTN_SHARED_MAX = 0, 1, 2   # cir_set_tuning knobs (tests / A-B only)
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
+class AdamwGroups(ctypes.Structure):
+    """cir_adamw_groups of include/cirrank.h: up to 8 (lr, weight_decay, eps) triples, passed to the kernel by value."""
+    _fields_ = [("lr", c_float * 8), ("weight_decay", c_float * 8), ("eps", c_float * 8)]
+
+
 class WgradDesc(ctypes.Structure):
     """cir_wgrad_desc of include/cirrank.h (one problem of cir_wgrad_grouped)."""
     _fields_ = [("dy", c_void_p), ("ldy", c_int64), ("x", c_void_p), ("ldx", c_int64), ("dw", c_void_p), ("ldw", c_int64), ("rows", c_int64),
@@ -118,6 +123,11 @@ SIGNATURES = {
     "cir_grads_check": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p]),
     "cir_adamw_begin": (c_int, [c_void_p, c_float, c_float, c_void_p]),
     "cir_adamw_step_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    "cir_grads_sumsq": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cir_grads_sumsq_workspace": (c_int64, [c_int64]),
+    "cir_adamw_begin_clip": (c_int, [c_void_p, c_float, c_float, c_void_p, c_int64, c_float, c_void_p]),
+    "cir_adamw_step_groups": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                      ctypes.POINTER(AdamwGroups), c_int, c_int, c_void_p, c_int, c_void_p]),
     # stage-I contrastive head (blip_stage1.py:83-91)
     "cir_contrastive_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "cir_contrastive_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,

@@ -37,7 +37,7 @@ import torch
 from . import ops, train_ops as T
 from .train_core import (Trainer, _Lin, _Lin2, _cast, _install_grads, _row_split, apply_pending_counters, load_training_state,  # noqa: F401
                          loss_scale, train_dtype, training_state)                                                             # (re-exported)
-from .train_optim import AdamW, cosine_lr_schedule  # noqa: F401  (re-exported)
+from .train_optim import AdamW, cosine_lr_schedule, exp_lr_schedule, step_lr_schedule, warmup_lr_schedule  # noqa: F401  (re-exported)
 from .train_ops import deterministic, set_deterministic  # noqa: F401  (re-exported: the deterministic training mode)
 from .train_vit import vit_checkpointed_blocks, vit_saved_bytes  # noqa: F401  (re-exported: ViT gradient checkpointing)
 
@@ -353,3 +353,29 @@ def fusion_train(model, z_t, feats, ids, mask, p_hidden: float = 0.1, p_attn: fl
         tr.anchor = torch.zeros((1,), device=z_t.device, requires_grad=True)
     tr.need_dfeats = bool(torch.is_tensor(feats) and feats.requires_grad)
     return _FusionTrainFn.apply(tr.anchor, tr, z_t, feats, ids, mask)
+
+
+_NO_DECAY_NAMES = ("visual_encoder.pos_embed", "visual_encoder.cls_token")
+
+
+def param_groups(model, weight_decay: float, lr_scale: Dict[str, float] = None) -> List[Dict]:
+    """Group dicts for `AdamW` (and torch.optim.AdamW) over the `requires_grad` parameters of `model`, in `named_parameters()` order:
+    biases, LayerNorm weights and every other parameter with ndim <= 1, plus visual_encoder.pos_embed / cls_token, take weight_decay 0
+    (the reference's single group, stage2_train.py:138, gives them the config's full 0.05); `lr_scale` = {name prefix: factor} - the first
+    prefix a name starts with, in the dict's order - splits further, e.g. {"visual_encoder.": 0.1} for a ViT tuned at a tenth of the rate.
+    A group carries "lr_scale" only when its factor is not 1; groups come in the order their first parameter appears; empty ones are left
+    out.  At most 8 groups (cir_adamw_step_groups)."""
+    scales = list((lr_scale or {}).items())
+    groups: Dict[tuple, Dict] = {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        scale = next((float(f) for prefix, f in scales if name.startswith(prefix)), 1.0)
+        decay = 0.0 if p.ndim <= 1 or name in _NO_DECAY_NAMES else float(weight_decay)
+        g = groups.get((decay, scale))
+        if g is None:
+            g = groups[(decay, scale)] = {"params": [], "weight_decay": decay}
+            if scale != 1.0:
+                g["lr_scale"] = scale
+        g["params"].append(p)
+    return list(groups.values())

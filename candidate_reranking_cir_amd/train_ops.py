@@ -445,6 +445,79 @@ def adamw_step_dev(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.T
     _lib.PARAM_EPOCH[0] += 1
 
 
+MAX_GROUPS = 8                            # CIR_ADAMW_MAX_GROUPS
+
+
+def grads_sumsq_workspace(n: int) -> int:
+    """The number of float64 partial sums grads_sumsq writes for a buffer of n elements (cir_grads_sumsq_workspace: host only)."""
+    k = int(_lib.load().cir_grads_sumsq_workspace(int(n)))
+    if k < 0:
+        _lib.check(k, "cir_grads_sumsq_workspace")
+    return k
+
+
+def grads_sumsq(g: torch.Tensor, state: torch.Tensor, partials: torch.Tensor):
+    """state[0] |= any non-finite element of g, partials[:grads_sumsq_workspace(n)] = per-workgroup float64 sums of squares; g is only
+    read (cir_grads_sumsq).  The norm pass of a clipped step: cir_adamw_begin_clip adds the partials of all its work items."""
+    _need_cuda(g, state, partials)
+    assert g.dtype == torch.float32 and g.is_contiguous() and state.dtype == torch.int32 and state.numel() >= 8
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= grads_sumsq_workspace(g.numel())
+    _lib.check(_lib.load().cir_grads_sumsq(g.data_ptr(), g.numel(), state.data_ptr(), partials.data_ptr(), _stream()), "cir_grads_sumsq")
+
+
+def adamw_begin_clip(state: torch.Tensor, betas, partials: torch.Tensor, max_norm: float):
+    """adamw_begin + clip_grad_norm_'s coefficient from ALL of `partials` (cir_adamw_begin_clip): state[5] = min(1, max_norm / (norm + 1e-6)),
+    state[6] = the fp32 global norm; a set flag skips the step and leaves coef = 0."""
+    _need_cuda(state, partials)
+    assert state.dtype == torch.int32 and state.numel() >= 8 and partials.dtype == torch.float64 and partials.is_contiguous()
+    _lib.check(_lib.load().cir_adamw_begin_clip(state.data_ptr(), float(betas[0]), float(betas[1]), partials.data_ptr(), partials.numel(), float(max_norm),
+                                                _stream()), "cir_adamw_begin_clip")
+
+
+class SegmentTable:
+    """The device half of cir_adamw_step_groups' segment table, checked on the host ONCE (the kernel cannot refuse a bad table): ascending
+    END offsets in elements, every end a multiple of 8 but the last (= n, a multiple of 4), one group id in 0..7 per segment."""
+
+    def __init__(self, ends, ids, device):
+        ends, ids = [int(e) for e in ends], [int(i) for i in ids]
+        if not ends or len(ends) != len(ids):
+            raise ValueError(f"segment table: {len(ends)} ends for {len(ids)} group ids")
+        if any(b <= a for a, b in zip([0] + ends, ends)) or any(e % 8 for e in ends[:-1]) or ends[-1] % 4:
+            raise ValueError("segment table: ends must ascend from above 0 in multiples of 8 (the last: a multiple of 4)")
+        if min(ids) < 0 or max(ids) >= MAX_GROUPS:
+            raise ValueError(f"segment table: group ids must lie in 0..{MAX_GROUPS - 1}")
+        self.n, self.nseg, self.max_id = ends[-1], len(ends), max(ids)
+        self.ends = torch.tensor(ends, dtype=torch.int64, device=device)
+        self.ids = torch.tensor(ids, dtype=torch.int32, device=device)
+
+
+def adamw_groups(groups) -> "_lib.AdamwGroups":
+    """[(lr, weight_decay, eps), ...] (at most 8) as the by-value kernel argument of cir_adamw_step_groups."""
+    if not 1 <= len(groups) <= MAX_GROUPS:
+        raise ValueError(f"adamw_step_groups takes 1 to {MAX_GROUPS} groups, not {len(groups)}")
+    a = _lib.AdamwGroups()
+    for k, (lr, wd, eps) in enumerate(groups):
+        a.lr[k], a.weight_decay[k], a.eps[k] = float(lr), float(wd), float(eps)
+    return a
+
+
+def adamw_step_groups(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, state: torch.Tensor, groups, betas=(0.9, 0.999),
+                      table: SegmentTable = None, group: int = 0, clip: bool = False, p16: torch.Tensor = None):
+    """adamw_step_dev with per-segment (lr, weight_decay, eps): `groups` = [(lr, wd, eps), ...]; `table` (a SegmentTable) maps element
+    ranges to groups, without one every element takes `group`; `clip`: g * state[5] in registers (cir_adamw_step_groups)."""
+    _need_cuda(p, g, m, v, state)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel() for t in (p, g, m, v))
+    assert p16 is None or (p16.is_contiguous() and p16.numel() == p.numel() and p16.dtype in (torch.float16, torch.bfloat16))
+    a = adamw_groups(groups)
+    if table is not None and (table.n != p.numel() or table.max_id >= len(groups) or table.ends.device != p.device):
+        raise ValueError(f"segment table for {table.n} elements / group ids up to {table.max_id}: the launch has {p.numel()} elements, {len(groups)} groups")
+    _lib.check(_lib.load().cir_adamw_step_groups(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(betas[0]), float(betas[1]),
+                                                 state.data_ptr(), None if table is None else table.ends.data_ptr(),
+                                                 None if table is None else table.ids.data_ptr(), 1 if table is None else table.nseg, int(group),
+                                                 ctypes.byref(a), len(groups), int(bool(clip)), None if p16 is None else p16.data_ptr(),
+                                                 0 if p16 is None else _DT[p16.dtype], _stream()), "cir_adamw_step_groups")
+    _lib.PARAM_EPOCH[0] += 1
+
 
 def contrastive_fwd(p: torch.Tensor, target: torch.Tensor, temp: torch.Tensor):
     """Stage-I contrastive head (cir_contrastive_fwd, blip_stage1.py:83-91): p (B, E), target (Bt, E) fp32 contiguous, temp the fp32 scalar

@@ -631,6 +631,46 @@ int cir_grads_check(float* g, int64_t n, float scale, int32_t* state, void* stre
 int cir_adamw_begin(int32_t* state, float beta1, float beta2, void* stream);
 int cir_adamw_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                        const int32_t* state, void* p16, int dtype16, void* stream);
+/* Parameter groups and clip_grad_norm_ on the same device state (additive within ABI 15).  The reference builds ONE group
+ * (stage2_train.py:138) and steps it under the scaler (:215-218); its schedules write every group's lr (utils.py:216-241).  A trained ViT
+ * beside the text encoders wants a lower rate for visual_encoder.*, no decay on biases / LayerNorm / pos_embed / cls_token, and a bound on
+ * the gradient norm - all decided where the gradients are, without a host read.  state[5] = fp32 clip coefficient, state[6] = fp32
+ * pre-clip norm of the step in flight; state[7] stays free.
+ *   cir_grads_sumsq            one read-only pass over g (n >= 1 fp32, 16-byte aligned): state[0] |= any non-finite element (cir_grads_check's
+ *                              test; state[1..7] untouched) and partials[b] = the float64 sum of squares workgroup b read.  Fixed order, no
+ *                              float atomics: the partials repeat bit for bit.  The grid is a function of n alone.
+ *   cir_grads_sumsq_workspace  pure host function: the number of doubles cir_grads_sumsq(n) writes (CIR_EINVAL for n < 1).
+ *   cir_adamw_begin_clip       cir_adamw_begin + the clip, after the norm passes of EVERY work item of the step wrote their partials side by
+ *                              side: total_norm = fp32(sqrt(sum of the n_partials doubles, in index order with a fixed tree)),
+ *                              coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 (torch.nn.utils.clip_grad_norm_), state[5] = coef,
+ *                              state[6] = total_norm.  Flag set: state[2] += 1, state[1] / [3] / [4] stay, state[6] = the norm as summed
+ *                              (inf / NaN possible), state[5] = 0.  max_norm finite and > 0 (CIR_EINVAL).
+ *   cir_adamw_step_groups      cir_adamw_step_dev with (lr, weight_decay, eps) per float4: `groups` holds up to CIR_ADAMW_MAX_GROUPS triples
+ *                              and travels BY VALUE as a kernel argument (a schedule that rewrites lr uploads nothing).  seg_end / seg_group:
+ *                              DEVICE arrays of nseg ascending segment END offsets in elements - every end a multiple of 8, the last = n -
+ *                              and one group id per segment (the trainers' slabs pad each parameter to 8 elements: no float4 straddles
+ *                              two parameters; the padding belongs to the segment before it).  Both NULL with nseg = 1: every element
+ *                              takes group `group` - the per-tensor form, the only one whose n may be no multiple of 4.  clip != 0:
+ *                              g is multiplied by state[5] in registers (one fp32 rounding); g itself is never written.  nseg = 1 without
+ *                              clip has the bits of cir_adamw_step_dev.  The table lives on the device, so this entry point CANNOT check
+ *                              it: a C caller gets no refusal for a bad table.  The kernel never reads outside the nseg entries and takes
+ *                              every id modulo 8; an id in ngroups..7 then selects a triple of `groups` the caller did not fill - with a
+ *                              zero-initialised struct lr = 0, weight_decay = 0, eps = 0: m and v are updated, p keeps its value (0 / 0 =
+ *                              NaN where v' is 0) - and ends that do not ascend or are no multiples of 8 give elements another segment's
+ *                              scalars.  Check the table where it is built, as train_ops.SegmentTable does on the host.
+ *                              CIR_EINVAL: nseg < 1, ngroups outside 1..8, `group` outside 0..ngroups-1, one of the two arrays NULL, a
+ *                              table with n % 4 != 0; CIR_EALIGN: p, g, m, v not 16-byte, p16 / seg_end not 8-byte, seg_group not 4-byte
+ *                              aligned; CIR_EDTYPE: p16 with a dtype16 other than CIR_F16 / CIR_BF16. */
+#define CIR_ADAMW_MAX_GROUPS 8
+typedef struct cir_adamw_groups {
+    float lr[CIR_ADAMW_MAX_GROUPS], weight_decay[CIR_ADAMW_MAX_GROUPS], eps[CIR_ADAMW_MAX_GROUPS];
+} cir_adamw_groups;
+int cir_grads_sumsq(const float* g, int64_t n, int32_t* state, double* partials, void* stream);
+int64_t cir_grads_sumsq_workspace(int64_t n);
+int cir_adamw_begin_clip(int32_t* state, float beta1, float beta2, const double* partials, int64_t n_partials, float max_norm, void* stream);
+int cir_adamw_step_groups(float* p, const float* g, float* m, float* v, int64_t n, float beta1, float beta2, const int32_t* state,
+                          const int64_t* seg_end, const int32_t* seg_group, int nseg, int group, const cir_adamw_groups* groups, int ngroups,
+                          int clip, void* p16, int dtype16, void* stream);
 /* Contrastive head of the stage-I training step (blip_stage1.py:83-91; driven by stage1_train.py:170-172):
  *   p_hat = F.normalize(p) = p / max(||p||, 1e-12),   logits = p_hat target^T / temp
  * p (B, E) fp32 = text_proj of the CLS rows; target (Bt, E) fp32, used as given (the reference's pooled target features are already
