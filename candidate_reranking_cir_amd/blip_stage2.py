@@ -524,6 +524,23 @@ class BLIP_NLVR(_EngineHost):
             logits = self.score(z, ids, mask, ops.gather_rows(cand, rows), qidx)
             return logits.view(b, b)
 
+    # ---- what a score rests on (explain.py; the reference's save_attention / get_attention_map / get_attn_gradients, nlvr_encoder.py:121-134)
+    def cross_attention_maps(self, r_image_embeds, t_image_embeds, text, layers, grads=True):
+        """`explain.cross_attention_maps`: B queries x Bt candidates -> CrossAttentionMaps(logits (B, Bt), probs / grads {layer: (2, B, Bt, H, L, N)})."""
+        from .explain import cross_attention_maps
+        return cross_attention_maps(self, r_image_embeds, t_image_embeds, text, layers, grads)
+
+    def gradcam(self, r_image_embeds, t_image_embeds, text, layer):
+        """`explain.gradcam`: (2, B, Bt, L, N) fp32, the head mean of probs * max(grads, 0) at fusion layer `layer`."""
+        from .explain import gradcam
+        return gradcam(self, r_image_embeds, t_image_embeds, text, layer)
+
+    @staticmethod
+    def patch_grid(x):
+        """`explain.patch_grid`: (..., N) -> (..., g, g) without the CLS key."""
+        from .explain import patch_grid
+        return patch_grid(x)
+
 
 def blip_stage2(pretrained: str = "", **kwargs) -> BLIP_NLVR:
     """Factory with the reference's signature (blip_stage2.py:139-145).  `pretrained` names a local BLIP base

@@ -1,5 +1,5 @@
 // The shared pieces of the "keys on rows" 32 x 32 tile update (attention.hip has the formulation): every attention kernel of
-// attention.hip, attention_f32.hip and train_attn.hip is built from these, so the V-tile swizzle, the transposed read and the
+// attention.hip, attention_f32.hip, train_attn.hip and attn_maps.hip is built from these, so the V-tile swizzle, the transposed read and the
 // accumulator's element map each exist once.  Device-only; nothing here launches or owns LDS.
 //
 // NOT here, on purpose: the softmax steps.  Four exist and they are four different computations:
@@ -14,6 +14,9 @@
 namespace cir {
 
 constexpr float kLog2e = 1.4426950408889634f;
+// the training kernels' mask clamp and the lse of a group whose every key sits at it (train_attn.hip has the account; attn_maps.hip shares them)
+constexpr float kMaskClamp = -2.0e38f;
+constexpr float kSatLse = kMaskClamp * kLog2e;                  // = fmaf(kMaskClamp, kLog2e, s) for every |s| < 1e30
 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
 // accumulator index i of a 32 x 32 tile -> row inside the tile (keys, for a score tile); this lane's column is lane & 31

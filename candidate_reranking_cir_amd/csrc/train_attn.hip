@@ -41,9 +41,8 @@ struct TAttnArgs {
 // (q.k is absorbed), the forward's rows are uniform over the Lk keys, and its lse = m + log2 l is the clamp again - log2 l is absorbed as
 // well, so exp2(s + mask - lse) cannot rebuild P = 1 / Lk (dQ was NaN, dK / dV Lk times too large).  The backward kernels recognise the
 // group by that lse - no other row can have it - and rebuild what the forward used: score scale 0, mask weight 0, -lse = -log2 Lk.  The mask
-// is the group's, so the condition is uniform over a wave; it costs nothing per element.
-constexpr float kMaskClamp = -2.0e38f;
-constexpr float kSatLse = kMaskClamp * kLog2e;                  // = fmaf(kMaskClamp, kLog2e, s) for every |s| < 1e30
+// is the group's, so the condition is uniform over a wave; it costs nothing per element.  (kMaskClamp / kSatLse: attn_tile.hpp - the
+// attention-map kernels of attn_maps.hip rebuild P from the same lse.)
 
 // gradient store of a transposed accumulator (same element map) at element offset `off` of `base`: fp32 or the operand type
 template <typename T>

@@ -95,6 +95,13 @@ SIGNATURES = {
                                         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                         c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_uint64, c_int, c_void_p]),
+    # attention maps of the fused training attention (csrc/attn_maps.hip; nlvr_encoder.py:199-203)
+    "cir_attention_maps": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                   c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                   c_int, c_float, c_float, c_int, c_void_p]),
+    "cir_attention_gradcam": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                      c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                      c_int, c_float, c_float, c_int, c_void_p]),
     "cir_residual_layernorm_train": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float,
                                              c_float, c_float, c_uint64, c_int, c_void_p]),
     "cir_layernorm_bwd_fused": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,

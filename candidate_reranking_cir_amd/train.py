@@ -30,7 +30,7 @@ update on `cir_adamw_step`.  The slab, the layer views and the trainer base both
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 
@@ -43,7 +43,9 @@ from .train_vit import vit_checkpointed_blocks, vit_saved_bytes  # noqa: F401  (
 
 
 class NlvrTrainer(Trainer):
-    """Forward (with saved activations) and backward of the two-branch encoder + cls_head for a B x B training batch."""
+    """Forward (with saved activations) and backward of the two-branch encoder + cls_head for a B x Bt training batch: B queries against Bt
+    target images (Bt = B: the reference's step; Bt > B: extra negatives; B = 1: one query against its candidates, the shape of
+    img_txt_fusion_val, which explain.py runs)."""
 
     _KEY, _NAME = "text", "img_txt_fusion (train mode)"
     # Slab order (train_core.slab_order): per layer the twin (branch 0 | branch 1) dense layers as adjacent groups - all weights of a group,
@@ -132,22 +134,22 @@ class NlvrTrainer(Trainer):
     # ------------------------------------------------------------------------------------------------ forward
     @torch.no_grad()
     def forward(self, z_t: torch.Tensor, feats: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
-        """z_t (B, L, D) fp32, feats (B, N, Dv), ids / mask (B, L) with [ENC] set -> logits (B, B) fp32; keeps what backward needs."""
+        """z_t (B, L, D) fp32, feats (Bt, N, Dv), ids / mask (B, L) with [ENC] set -> logits (B, Bt) fp32; keeps what backward needs."""
         self._pack()
         self.step_no += 1
         g, dt, dev = self.geo, self.dtype, z_t.device
         b_n, l = input_ids.shape
-        n, d = feats.shape[1], g.hidden_size
-        t_n = b_n * b_n
+        bt_n, n, d = feats.shape[0], feats.shape[1], g.hidden_size
+        t_n = b_n * bt_n
         r = t_n * l
         ph = self.p_hidden
         f32 = torch.float32
         # triplet t = j * B + i scores query i (caption, z_t) against target j - candidate-major, so that the B queries of one
         # target are consecutive rows and its cross-attention keys / values are projected ONCE (the reference recomputes them
-        # for every query, blip_stage2.py:80-92; same values); the (B_j, B_i) result is transposed on the way out
-        qi = torch.arange(b_n, device=dev).repeat(b_n)
+        # for every query, blip_stage2.py:80-92; same values); the (Bt_j, B_i) result is transposed on the way out
+        qi = torch.arange(b_n, device=dev).repeat(bt_n)
         ids_t = input_ids.to(dev)[qi].contiguous()                                  # (T, L)
-        self.sv = sv = {"ids": ids_t, "t_n": t_n, "l": l, "n": n, "b_n": b_n}
+        self.sv = sv = {"ids": ids_t, "t_n": t_n, "l": l, "n": n, "b_n": b_n, "bt_n": bt_n}
         # embeddings (BertEmbeddings: LayerNorm(word + pos), dropout) -> branch 1; z_t -> branch 0 (nlvr_encoder.py:880-892)
         pos_idx = torch.arange(l, device=dev).repeat(t_n)
         pre_e = T.eltwise(ops.gather_rows(self.word, ids_t.view(-1), f32), T.MODE_ADD, ops.gather_rows(self.pos, pos_idx, f32))
@@ -160,9 +162,9 @@ class NlvrTrainer(Trainer):
         h32[0].copy_(ops.gather_rows(z_t.to(dev).float().contiguous().view(b_n, l * d), qi, f32).view(r, d))
         h32[1].copy_(e32)
         h16 = _cast(h32, dt)
-        cand16 = _cast(feats.to(dev).float().contiguous(), dt).view(b_n * n, -1)                          # (B*N, Dv): each target once
+        cand16 = _cast(feats.to(dev).float().contiguous(), dt).view(bt_n * n, -1)                         # (Bt*N, Dv): each target once
         sv["cand16"] = cand16
-        cand2 = cand16.unsqueeze(0).expand(2, b_n * n, cand16.shape[1])                                   # one input, two branches (batch stride 0)
+        cand2 = cand16.unsqueeze(0).expand(2, bt_n * n, cand16.shape[1])                                   # one input, two branches (batch stride 0)
         smask = ((1.0 - attention_mask.to(dev).float()) * -10000.0)[qi].contiguous()                      # (T, L), nlvr_encoder.py:773-774
         smask2 = smask.repeat(2, 1)                                                                       # the same key masks for both branches' groups
         sv["layers"] = []
@@ -185,8 +187,8 @@ class NlvrTrainer(Trainer):
             c = torch.empty((2, r, d), dtype=dt, device=dev)
             c32 = torch.empty((2, r, d), dtype=f32, device=dev)
             # ... and both cross-attentions: group = (branch, target image), its B * L stacked query rows against the target's 577 keys
-            kv2 = ckv.view(2 * b_n * n, 2 * d)
-            s["ca"] = self._attn_fwd(self._heads(cq.view(2 * r, d), 2 * b_n, b_n * l), self._heads(kv2, 2 * b_n, n, 0, 2), self._heads(kv2, 2 * b_n, n, 1, 2),
+            kv2 = ckv.view(2 * bt_n * n, 2 * d)
+            s["ca"] = self._attn_fwd(self._heads(cq.view(2 * r, d), 2 * bt_n, b_n * l), self._heads(kv2, 2 * bt_n, n, 0, 2), self._heads(kv2, 2 * bt_n, n, 1, 2),
                                      None, self._site(i, 0, 3), c.view(2 * r, d), c32.view(2 * r, d))
             if ly["merge"] is None:                                                 # layers < 6: average (nlvr_encoder.py:257-260)
                 dd = ly["d"].fwd(c, f32)
@@ -217,17 +219,23 @@ class NlvrTrainer(Trainer):
         y16 = T.eltwise(z1, T.MODE_RELU, out_dtype=dt)
         logits2 = self.c2.fwd(y16, f32)                                             # (T, 2)
         sv.update(hid16=hid16, z1=z1, y16=y16, cls_rows=cls_rows)
-        return logits2[:, 0].contiguous().view(b_n, b_n).t().contiguous()           # (B_j, B_i) -> (B_i, B_j)
+        return logits2[:, 0].contiguous().view(bt_n, b_n).t().contiguous()          # (Bt_j, B_i) -> (B_i, Bt_j)
 
     def head_mask(self) -> torch.Tensor:
-        """(B*B, hidden) bool: which cls_head.0 units were active in the last forward, rows in the reference's order (i * B + j)."""
-        b = self.sv["b_n"]
-        return (self.sv["z1"] > 0).view(b, b, -1).transpose(0, 1).reshape(b * b, -1)
+        """(B*Bt, hidden) bool: which cls_head.0 units were active in the last forward, rows in the reference's order (i * Bt + j)."""
+        b, bt = self.sv["b_n"], self.sv["bt_n"]
+        return (self.sv["z1"] > 0).view(bt, b, -1).transpose(0, 1).reshape(b * bt, -1)
 
     # ------------------------------------------------------------------------------------------------ backward
     @torch.no_grad()
-    def backward(self, dlogits: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """dlogits (B, B) fp32 -> {parameter name: fp32 gradient} for every text_encoder.* / cls_head.* parameter."""
+    def backward(self, dlogits: torch.Tensor, observer=None) -> Optional[Dict[str, torch.Tensor]]:
+        """dlogits (B, Bt) fp32 -> {parameter name: fp32 gradient} for every text_encoder.* / cls_head.* parameter.
+
+        `observer` (None by default: the pass is then the same launches with the same arguments) is called at the cross-attention adjoint
+        of each layer, top layer first, as observer(layer, dc16, q4, k4, v4, saved): dc16 (2, R, D) the 16-bit gradient of the context
+        (times `self.grad_scale`), q4 (2 Bt, H, B L, hd) / k4 / v4 (2 Bt, H, N, hd) the head views the adjoint is about to read (group =
+        (branch, target), rows = (query, token)), saved = what `_attn_fwd` returned (lse first).  A true return value ends the reverse
+        pass there - the observer needs nothing below that layer - and backward returns None: the gradient buffer is then incomplete."""
         sv, g, dt = self.sv, self.geo, self.dtype
         det = self.slab.read_mode()                                                 # {} or the fixed-order forms' workspace (deterministic mode)
         dev = dlogits.device
@@ -250,8 +258,8 @@ class NlvrTrainer(Trainer):
         dh = torch.zeros((2 * r, d), dtype=torch.float32, device=dev)               # both branches stacked, as the FFN saw them
         dh[sv["cls_rows"]] = dhid[:, :d]
         dh[sv["cls_rows"] + r] = dhid[:, d:]
-        ph, b_n = self.p_hidden, sv["b_n"]
-        dfeats = torch.empty((b_n * n, sv["cand16"].shape[1]), dtype=torch.float32, device=dev) if self.need_dfeats else None
+        ph, b_n, bt_n = self.p_hidden, sv["b_n"], sv["bt_n"]
+        dfeats = torch.empty((bt_n * n, sv["cand16"].shape[1]), dtype=torch.float32, device=dev) if self.need_dfeats else None
         dfeats_live = False
         for i in reversed(range(len(self.layers))):
             ly, s = self.layers[i], sv["layers"][i]
@@ -279,12 +287,14 @@ class NlvrTrainer(Trainer):
             dc16 = ly["d"].dgrad(dd16, dt)                                          # (2, R, D): both branches' output-dense dgrads, one GEMM
             cq, ckv = s["cq"], s["ckv"]
             dcq16 = torch.empty((2, r, d), dtype=dt, device=dev)
-            dckv16 = torch.empty((2, b_n * n, 2 * d), dtype=dt, device=dev)
-            kv2, dkv2 = ckv.view(2 * b_n * n, 2 * d), dckv16.view(2 * b_n * n, 2 * d)
-            self._attn_bwd(dc16.view(2 * r, d), self._heads(cq.view(2 * r, d), 2 * b_n, b_n * l), self._heads(kv2, 2 * b_n, n, 0, 2),
-                           self._heads(kv2, 2 * b_n, n, 1, 2), s["ca"], self._heads(dcq16.view(2 * r, d), 2 * b_n, b_n * l),
-                           self._heads(dkv2, 2 * b_n, n, 0, 2), self._heads(dkv2, 2 * b_n, n, 1, 2))
-            cand2 = sv["cand16"].unsqueeze(0).expand(2, b_n * n, sv["cand16"].shape[1])
+            dckv16 = torch.empty((2, bt_n * n, 2 * d), dtype=dt, device=dev)
+            kv2, dkv2 = ckv.view(2 * bt_n * n, 2 * d), dckv16.view(2 * bt_n * n, 2 * d)
+            cq4, ck4, cv4 = self._heads(cq.view(2 * r, d), 2 * bt_n, b_n * l), self._heads(kv2, 2 * bt_n, n, 0, 2), self._heads(kv2, 2 * bt_n, n, 1, 2)
+            if observer is not None and observer(i, dc16, cq4, ck4, cv4, s["ca"]):
+                return None
+            self._attn_bwd(dc16.view(2 * r, d), cq4, ck4, cv4, s["ca"], self._heads(dcq16.view(2 * r, d), 2 * bt_n, b_n * l),
+                           self._heads(dkv2, 2 * bt_n, n, 0, 2), self._heads(dkv2, 2 * bt_n, n, 1, 2))
+            cand2 = sv["cand16"].unsqueeze(0).expand(2, bt_n * n, sv["cand16"].shape[1])
             ly["ckv"].wgrad(cand2, dckv16, wq, bias=True)
             if dfeats is not None:                                                  # ViT fine-tuning: every layer and branch adds its share
                 for b in (0, 1):                                                    # (image tokens are inputs otherwise: no gradient beyond the weights)
@@ -339,18 +349,26 @@ class _FusionTrainFn(torch.autograd.Function):
         return None, None, None, dfeats, None, None
 
 
-def fusion_train(model, z_t, feats, ids, mask, p_hidden: float = 0.1, p_attn: float = 0.1, seed: int = 0) -> torch.Tensor:
-    """(B, B) logits of `img_txt_fusion` in training mode, differentiable w.r.t. the model's text_encoder / cls_head parameters - and
-    w.r.t. the target image tokens when they require a gradient (blip_img_tune, stage2_train.py:191-199: the tokens then come from
-    `train_vit.vit_train`, whose reverse pass continues into the ViT)."""
-    if torch.is_tensor(z_t) and z_t.requires_grad:
-        raise NotImplementedError("z_t requires a gradient: the reference computes it from the frozen stage-I model under torch.no_grad() "
-                                  "(stage2_train.py:201-203); the backward pass stops at the two-branch encoder's z_t input")
+def model_trainer(model, p_hidden: float, p_attn: float, seed: int, device) -> NlvrTrainer:
+    """The model's one NlvrTrainer (`model._trainer`: one slab - a second one would re-point every parameter), rebuilt when the dropout
+    probabilities or the operand type changed."""
     tr = getattr(model, "_trainer", None)
     if tr is None or (tr.p_hidden, tr.p_attn) != (float(p_hidden), float(p_attn)) or tr.dtype != train_dtype(model):
         tr = model._trainer = NlvrTrainer(model, p_hidden, p_attn, seed)
         apply_pending_counters(model, "fusion", tr)           # (seed, step_no) a checkpoint left for this trainer (load_training_state)
-        tr.anchor = torch.zeros((1,), device=z_t.device, requires_grad=True)
+        tr.anchor = torch.zeros((1,), device=device, requires_grad=True)
+    return tr
+
+
+def fusion_train(model, z_t, feats, ids, mask, p_hidden: float = 0.1, p_attn: float = 0.1, seed: int = 0) -> torch.Tensor:
+    """(B, Bt) logits of `img_txt_fusion` in training mode (z_t / ids / mask: B queries; feats: Bt targets - Bt = B is the reference's step,
+    Bt > B adds negatives), differentiable w.r.t. the model's text_encoder / cls_head parameters - and w.r.t. the target image tokens when
+    they require a gradient (blip_img_tune, stage2_train.py:191-199: the tokens then come from `train_vit.vit_train`, whose reverse pass
+    continues into the ViT)."""
+    if torch.is_tensor(z_t) and z_t.requires_grad:
+        raise NotImplementedError("z_t requires a gradient: the reference computes it from the frozen stage-I model under torch.no_grad() "
+                                  "(stage2_train.py:201-203); the backward pass stops at the two-branch encoder's z_t input")
+    tr = model_trainer(model, p_hidden, p_attn, seed, z_t.device)
     tr.need_dfeats = bool(torch.is_tensor(feats) and feats.requires_grad)
     return _FusionTrainFn.apply(tr.anchor, tr, z_t, feats, ids, mask)
 

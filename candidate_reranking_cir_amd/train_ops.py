@@ -219,6 +219,52 @@ def attention_train_bwd(q4, k4, v4, mask, out4, dout4, lse, dq4, dk4, dv4, scale
                                                    int(seed) & (2 ** 63 - 1), _DT[q4.dtype], _stream()), "cir_attention_train_bwd")
 
 
+def _maps_args(q4, k4, v4, mask, dout4, lse):
+    """Checks and marshalling shared by `attention_maps` / `attention_gradcam`: (G, H, Lq, Lk, ldk, leading C arguments)."""
+    _need_cuda(q4, k4, v4, mask, dout4, lse)
+    g, h, lq, hd = q4.shape
+    lk = k4.shape[2]
+    assert k4.shape == (g, h, lk, hd) and q4.dtype == k4.dtype
+    assert lse.shape == (g, h, lq) and lse.is_contiguous() and lse.dtype == torch.float32
+    if mask is not None:
+        assert mask.dtype == torch.float32 and mask.shape == (g, lk) and mask.is_contiguous()
+    if v4 is not None:
+        assert v4.shape == k4.shape and dout4.shape == q4.shape and v4.dtype == dout4.dtype == q4.dtype
+    none = (None, 0, 0, 0)
+    head = (*_hv(q4), *_hv(k4), *(none if v4 is None else _hv(v4)), _ptr(mask), *(none if dout4 is None else _hv(dout4)), lse.data_ptr())
+    return g, h, lq, lk, (lk + 3) // 4 * 4, head
+
+
+def attention_maps(q4: torch.Tensor, k4: torch.Tensor, v4: Optional[torch.Tensor], mask: Optional[torch.Tensor], dout4: Optional[torch.Tensor],
+                   lse: torch.Tensor, dmul: float = 1.0, grads: bool = True, scale: Optional[float] = None):
+    """The attention maps of `attention_train_fwd` (cir_attention_maps; nlvr_encoder.py:199-203): probs (G, H, Lq, Lk) fp32 - the
+    probabilities after the softmax and before the dropout, rebuilt from q4, k4, mask and the forward's `lse` - and, with `grads`,
+    dprobs = dmul * dout4 v4^T, the gradient of whatever `dout4` is the context's gradient of w.r.t. those probabilities.  Returns
+    (probs, dprobs | None): views (last dimension sliced to Lk) of buffers whose rows are Lk rounded up to 4 long.  `scale`: the softmax
+    scale of the forward (default: head dimension ** -0.5)."""
+    scale = q4.shape[3] ** -0.5 if scale is None else scale
+    if not grads:
+        v4 = dout4 = None
+    g, h, lq, lk, ldk, head = _maps_args(q4, k4, v4, mask, dout4, lse)
+    probs = torch.empty((g, h, lq, ldk), dtype=torch.float32, device=q4.device)
+    dprobs = torch.empty_like(probs) if grads else None
+    _lib.check(_lib.load().cir_attention_maps(*head, probs.data_ptr(), _ptr(dprobs), ldk, g, h, lq, lk, q4.shape[3], float(scale), float(dmul),
+                                              _DT[q4.dtype], _stream()), "cir_attention_maps")
+    return probs[..., :lk], (dprobs[..., :lk] if grads else None)
+
+
+def attention_gradcam(q4: torch.Tensor, k4: torch.Tensor, v4: torch.Tensor, mask: Optional[torch.Tensor], dout4: torch.Tensor, lse: torch.Tensor,
+                      dmul: float = 1.0, scale: Optional[float] = None) -> torch.Tensor:
+    """Grad-CAM of the same maps (cir_attention_gradcam): cam (G, Lq, Lk) fp32 = mean over the heads of probs * max(dprobs, 0), summed in
+    registers in a fixed order - no (G, H, Lq, Lk) tensor exists, and two calls return the same bits."""
+    scale = q4.shape[3] ** -0.5 if scale is None else scale
+    g, h, lq, lk, ldk, head = _maps_args(q4, k4, v4, mask, dout4, lse)
+    cam = torch.empty((g, lq, ldk), dtype=torch.float32, device=q4.device)
+    _lib.check(_lib.load().cir_attention_gradcam(*head, cam.data_ptr(), ldk, g, h, lq, lk, q4.shape[3], float(scale), float(dmul),
+                                                 _DT[q4.dtype], _stream()), "cir_attention_gradcam")
+    return cam[..., :lk]
+
+
 def layernorm_bwd(x: torch.Tensor, gamma: torch.Tensor, dy: torch.Tensor, dgamma: torch.Tensor, dbeta: torch.Tensor, eps: float,
                   work: Optional[Workspace] = None, dx: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x, dy fp32 (rows, cols) contiguous; dgamma / dbeta fp32 (cols) are ACCUMULATED into -> dx fp32 (may be given: a contiguous row

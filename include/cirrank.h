@@ -514,6 +514,29 @@ int cir_attention_train_bwd(const void* q, int64_t q_sg, int64_t q_sh, int64_t q
                             int64_t dq_sh, int64_t dq_sr, void* dk, int64_t dk_sg, int64_t dk_sh, int64_t dk_sr, void* dv, int64_t dv_sg,
                             int64_t dv_sh, int64_t dv_sr, int grad_dtype, int G, int H, int Lq, int Lk, float scale, float p_drop, uint64_t seed,
                             int dtype, void* stream);
+/* Attention MAPS of the fused training attention (csrc/attn_maps.hip; two entry points, additive within ABI v15: 72 in all): what
+ * nlvr_encoder.py:199-203 keeps when save_attention is set - attention_probs after the softmax and BEFORE the dropout (save_attention_map)
+ * and the gradient its register_hook receives (save_attn_gradients) - rebuilt tile by tile from q, k and the forward's log2-domain lse
+ * (cir_attention_train_fwd; p_drop = 0 there or not: the maps are the pre-dropout quantities) and written out as fp32:
+ *   probs  (G, H, Lq, ldk) = exp2(q k^T * scale * log2e + mask * log2e - lse)       (the kSatLse rule of cir_attention_train_bwd applies)
+ *   dprobs (G, H, Lq, ldk) = dmul * d_o v^T                                          (dmul: e.g. the inverse of a loss scale, a power of two)
+ * Tensors are head views as in cir_attention_train_bwd (element (g, h, row, d) at base + g * x_sg + h * x_sh + row * x_sr + d, strides
+ * multiples of 8, 16-byte aligned bases); mask fp32 (G, Lk) additive or NULL; lse fp32 (G, H, Lq).  v, d_o and dprobs are all NULL
+ * (probabilities only - the same bits as the full call's probs) or all non-NULL.  Row pitch ldk: ldk % 4 == 0, ldk >= Lk; columns
+ * [Lk, ldk) of every row are written with 0 and nothing outside the G * H * Lq * ldk elements is touched.  head_dim must be 64.
+ * CIR_ESHAPE: a bad ldk, head_dim != 64, an inconsistent NULL pattern.  16-bit operands (CIR_BF16 / CIR_F16).  Plain vector stores. */
+int cir_attention_maps(const void* q, int64_t q_sg, int64_t q_sh, int64_t q_sr, const void* k, int64_t k_sg, int64_t k_sh, int64_t k_sr,
+                       const void* v, int64_t v_sg, int64_t v_sh, int64_t v_sr, const float* mask, const void* d_o, int64_t o_sg,
+                       int64_t o_sh, int64_t o_sr, const float* lse, float* probs, float* dprobs, int64_t ldk, int G, int H, int Lq, int Lk,
+                       int head_dim, float scale, float dmul, int dtype, void* stream);
+/* Grad-CAM of the same maps without materialising them (nlvr_encoder.py:199-203 are the two factors):
+ *   cam (G, Lq, ldk) = (1 / H) sum_h probs[g, h] * max(dprobs[g, h], 0)
+ * one wave per (group, query tile, key tile) sums the heads in the order 0 .. H-1 in fp32 registers: no atomics, the result repeats bit for
+ * bit.  Same inputs (v and d_o required), checks and pad rule (columns [Lk, ldk) = 0) as cir_attention_maps. */
+int cir_attention_gradcam(const void* q, int64_t q_sg, int64_t q_sh, int64_t q_sr, const void* k, int64_t k_sg, int64_t k_sh, int64_t k_sr,
+                          const void* v, int64_t v_sg, int64_t v_sh, int64_t v_sr, const float* mask, const void* d_o, int64_t o_sg,
+                          int64_t o_sh, int64_t o_sr, const float* lse, float* cam, int64_t ldk, int G, int H, int Lq, int Lk, int head_dim,
+                          float scale, float dmul, int dtype, void* stream);
 /* LayerNorm backward from the saved fp32 input x of the forward: dx (written), dgamma / dbeta (fp32, ACCUMULATED atomically). */
 int cir_layernorm_bwd(const float* x, const float* gamma, const float* dy, float* dx, float* dgamma, float* dbeta, int64_t rows, int cols,
                       float eps, void* stream);
